@@ -11,7 +11,12 @@ SUM-all-reduced over RCCL every step (weak scaling: value = all ranks' rows / ma
 `python bench.py --gpus N` without a torchrun environment launches the N ranks itself (a child
 `torch.distributed.run` process; this parent never touches the GPU) and exits with its code.
 
-Also reported (extra fields, not `value`): sampling throughput of `--mode sample` for the v1 preset
+A plain run does only that: set up, warm up, time `--steps` steps, print the result line (with the
+live-timed roofline entries of those same steps). `--dump-outputs DIR` also writes what the last
+timed step left its caller (losses, and a fixed seeded sample of the gradients, parameters and Adam
+moments) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+With `--full`, also reported (extra fields, not `value`): sampling throughput of `--mode sample` for the v1 preset
 (C3: 1e6 genomes from a v1 checkpoint trained on the synthetic matrix, decoded with the output layer
 gated per 256 x 256 tile between one bf16 product over the rounded operands (the single tier), the
 bf16x3 split and exact fp32, the certified band recomputed in fp64 (a list overflow recomputes its
@@ -89,6 +94,12 @@ def parse():
     ap.add_argument("--hidden", type=int, default=1024)
     ap.add_argument("--latent", type=int, default=64)
     ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run every other leg (C5, v1-v3 presets, C1, the other "
+                         "precision, the sample leg, the CPU baselines); the --no-* options below drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses; a fixed seeded sample of the gradients, "
+                         "parameters, Adam moments; BatchNorm running statistics) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sample", action="store_true")
     ap.add_argument("--sample-genomes", type=int, default=1000000)
@@ -253,8 +264,33 @@ def scalar_table(nsteps, preset="v0", n_epochs=10000):
     return tab
 
 
+DUMP_SAMPLE = 1 << 16   # elements kept of each parameter tensor larger than this (--dump-outputs)
+
+
+def dump_outputs(path, model, opt, grads, losses):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy: `loss` (its
+    LOSS_SLOTS float64 record: BCE, sum p, KL, ..., gradient norm), `bn` (the BatchNorm running
+    statistics, whole) and, at one fixed index set, float32 `grads`, `params`, `exp_avg`, `exp_avg_sq`.
+    The index set (`index`.npy, float64) takes every parameter tensor of at most DUMP_SAMPLE elements
+    whole and a seeded DUMP_SAMPLE-element sample of each larger one: under 2 M elements per array."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.Generator(np.random.PCG64(2024))
+    idx = []
+    for lo, hi in zip(model.offsets[:-1], model.offsets[1:]):
+        n = hi - lo
+        idx.append(lo + (np.arange(n) if n <= DUMP_SAMPLE else np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))))
+    idx = np.concatenate(idx).astype(np.int64)
+    sel = torch.from_numpy(idx).to(grads.device)
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "loss.npy"), np.asarray(losses[-1], np.float64))
+    np.save(os.path.join(path, "bn.npy"), model.bn.detach().float().cpu().numpy())
+    for name, t in (("grads", grads), ("params", model.params), ("exp_avg", opt.exp_avg),
+                    ("exp_avg_sq", opt.exp_avg_sq)):
+        np.save(os.path.join(path, name + ".npy"), t.detach()[sel].float().cpu().numpy())
+
+
 def train_leg(a, dev, dist, rank, world, G, H, L, B, strains, prec, seed_base=12345, preset="v0", x=None,
-              steps=None, warmup=None):
+              steps=None, warmup=None, dump=None):
     """K timed training steps of `preset` (v0 unless given; after W warm-up steps) of `B` rows per
     rank, on a resident synthetic pan-genome shard of `strains` x G per rank (or the given host
     matrix x): forward, fused loss, backward, (bucketed all-reduce when world > 1), clip statistics
@@ -362,6 +398,8 @@ def train_leg(a, dev, dist, rank, world, G, H, L, B, strains, prec, seed_base=12
     bad = ~np.isfinite(losses[:, [0, 1, 2, 4]]).all(axis=1)
     if bad.any():
         raise RuntimeError(f"non-finite loss / gradient norm at step(s) {np.flatnonzero(bad).tolist()}")
+    if dump is not None and rank == 0:
+        dump_outputs(dump, model, opt, grads, losses)
     info = {"prefetch": prefetch, "input_chunks": ws.get_option(native.OPT_INPUT_CHUNKS),
             "defer_adam": ws.get_option(native.OPT_DEFER_OUTPUT_ADAM),
             "grad_buckets": ws.get_option(native.OPT_GRAD_BUCKETS),
@@ -412,6 +450,10 @@ def adam_roofline(a, ad):
 
 def main():
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if not a.full:  # a plain run: the headline steps only
+        a.no_c5 = a.no_presets = a.no_c1 = a.no_f32_line = a.no_sample = a.no_cpu_baseline = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -437,7 +479,7 @@ def main():
 
     G, H, L, B = a.genes, a.hidden, a.latent, a.batch
     prec = native.GM2_BF16 if a.precision == "bf16" else native.GM2_F32
-    elapsed, k_ms, k_n, info = train_leg(a, dev, dist, rank, world, G, H, L, B, a.strains, prec)
+    elapsed, k_ms, k_n, info = train_leg(a, dev, dist, rank, world, G, H, L, B, a.strains, prec, dump=a.dump_outputs)
     value = world * B * a.steps / elapsed
     out = {
         "metric": "strain-vectors/sec (train+sample), v0 preset, 1/2/4/8 MI355X vs host CPU",

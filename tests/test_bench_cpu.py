@@ -14,6 +14,48 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def test_plain_and_full_options(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--no-sample"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_sample and not a.no_c5
+
+
+def test_dump_outputs_index_set(tmp_path):
+    """--dump-outputs: small parameter tensors whole, a fixed DUMP_SAMPLE-element sample of each larger
+    one (sorted, no repeats, the same on every call), float32 / float64 files only."""
+    import types
+
+    import torch
+
+    import bench
+    big = bench.DUMP_SAMPLE + 1000
+    off = [0, 5, 5 + big, 5 + big + 70]
+    n = off[-1]
+    flat = lambda s: torch.arange(n, dtype=torch.float32) + s  # noqa: E731
+    model = types.SimpleNamespace(offsets=off, params=flat(0.0), bn=torch.ones(2, 2, 3))
+    opt = types.SimpleNamespace(exp_avg=flat(0.25), exp_avg_sq=flat(0.5))
+    losses = np.arange(12, dtype=np.float64).reshape(2, 6)
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), model, opt, flat(0.75), losses)
+        outs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert sorted(a) == ["bn", "exp_avg", "exp_avg_sq", "grads", "index", "loss", "params"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k])
+    idx = a["index"].astype(np.int64)
+    assert len(idx) == 5 + bench.DUMP_SAMPLE + 70 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx[:5], np.arange(5)) and np.array_equal(idx[-70:], np.arange(n - 70, n))
+    assert idx[5] >= 5 and idx[-71] < 5 + big
+    assert np.array_equal(a["loss"], losses[-1]) and a["bn"].shape == (2, 2, 3)
+    for k, s in (("params", 0.0), ("exp_avg", 0.25), ("exp_avg_sq", 0.5), ("grads", 0.75)):
+        assert np.array_equal(a[k], (idx + s).astype(np.float32))
+
+
 def test_preset_scalar_tables():
     import bench
     from gm2 import native

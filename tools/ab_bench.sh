@@ -2,10 +2,10 @@
 # Same-box A/B of bench.py flag sets: runs each variant R times alternately (short training-only bench).
 #   bash tools/ab_bench.sh TAG R "ARGS_A" "ARGS_B" ...     (a variant "VAR=x VAR2=y|ARGS" sets env too)
 cd "$GRAFT_REPO_ROOT" || exit 2
-mkdir -p gpurun_out
+OUT=${GM2_OUT:-bench_out}; mkdir -p "$OUT"
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 T=$1; R=$2; shift 2
-out=gpurun_out/ab_$T.log
+out=$OUT/ab_$T.log
 : > $out
 for r in $(seq 1 $R); do
   i=0

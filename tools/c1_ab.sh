@@ -2,12 +2,12 @@
 # Same-box A/B of bench.py flag sets on the C2 line and the c1_gpu (batch 64 / 32) lines.
 #   bash tools/c1_ab.sh TAG R "ARGS_A" "ARGS_B" ...
 cd "$GRAFT_REPO_ROOT" || exit 2
-mkdir -p gpurun_out
+OUT=${GM2_OUT:-bench_out}; mkdir -p "$OUT"
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 T=$1; R=$2; shift 2
-out=gpurun_out/c1ab_$T.log
+out=$OUT/c1ab_$T.log
 : > $out
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5 --no-presets"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5 --no-presets"
 for r in $(seq 1 $R); do
   i=0
   for v in "$@"; do

@@ -2,12 +2,12 @@
 # Same-box A/B of process environments (A/B switches read by libgm2) on the C2 line and the c1_gpu lines.
 #   bash tools/c1_env_ab.sh TAG R "VAR=x" "VAR=y" ...     ("-" = no variable)
 cd "$GRAFT_REPO_ROOT" || exit 2
-mkdir -p gpurun_out
+OUT=${GM2_OUT:-bench_out}; mkdir -p "$OUT"
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 T=$1; R=$2; shift 2
-out=gpurun_out/c1env_$T.log
+out=$OUT/c1env_$T.log
 : > $out
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5"
 for r in $(seq 1 $R); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then ev=""; else ev=$v; fi

@@ -9,13 +9,16 @@
     the kernel's algorithmic MFMA count where it is known;
   * HBM bytes per launch from separate FETCH_SIZE / WRITE_SIZE passes (FETCH_SIZE x2 on gfx950).
 
-Usage: python3 tools/kstats.py TAG [out.json|-] [timed steps]   (reads gpurun_out/{prof,pmc_mfma,pmc_fetch,pmc_write}_TAG)
+Usage: python3 tools/kstats.py TAG [out.json|-] [timed steps]   (reads $GM2_OUT/{prof,pmc_mfma,pmc_fetch,pmc_write}_TAG)
 """
 import collections
 import csv
 import json
+import os
 import re
 import sys
+
+OUT = os.environ.get("GM2_OUT", "bench_out")  # the folder the tools/*.sh runs write to
 
 
 def short(name):
@@ -41,7 +44,7 @@ def counters(d, with_grid=False):
 
 
 def step_breakdown(tag, steps):
-    rows = trace(f"gpurun_out/prof_{tag}")
+    rows = trace(OUT + f"/prof_{tag}")
     recon = [i for i, r in enumerate(rows) if "k_gemm_recon_loss" in r["Kernel_Name"]]
     # the timed steps of a C2-only run (bench.py --no-c5): from the `steps`-th last gather (a step's
     # first kernel) to the end of the last Adam launch (the final join's deferred output-layer update)
@@ -62,7 +65,7 @@ def step_breakdown(tag, steps):
 
 def mfma(tag):
     try:
-        c, names = counters(f"gpurun_out/pmc_mfma_{tag}")
+        c, names = counters(OUT + f"/pmc_mfma_{tag}")
     except FileNotFoundError:
         return {}
     per = collections.defaultdict(list)
@@ -78,7 +81,7 @@ def traffic(tag):
     out = {}
     for kind, scale in (("fetch", 2.0), ("write", 1.0)):
         try:
-            c, names = counters(f"gpurun_out/pmc_{kind}_{tag}", with_grid=True)
+            c, names = counters(OUT + f"/pmc_{kind}_{tag}", with_grid=True)
         except FileNotFoundError:
             continue
         per = collections.defaultdict(list)

@@ -2,12 +2,12 @@
 # Same-box A/B of bench.py flag sets on the C2 line and the v1 / v2 / v3 preset lines.
 #   bash tools/preset_ab.sh TAG R "ARGS_A" "ARGS_B" ...
 cd "$GRAFT_REPO_ROOT" || exit 2
-mkdir -p gpurun_out
+OUT=${GM2_OUT:-bench_out}; mkdir -p "$OUT"
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 T=$1; R=$2; shift 2
-out=gpurun_out/presetab_$T.log
+out=$OUT/presetab_$T.log
 : > $out
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5 --no-c1"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-line --no-sample --no-c5 --no-c1"
 for r in $(seq 1 $R); do
   i=0
   for v in "$@"; do

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Print the kernel timeline of the last full training step of a rocprofv3 kernel trace
-(gpurun_out/prof_TAG/run_kernel_trace.csv): start/end relative to the step, queue, grid, name."""
+($GM2_OUT/prof_TAG/run_kernel_trace.csv): start/end relative to the step, queue, grid, name."""
 import csv
+import os
 import re
 import sys
 
-rows = list(csv.DictReader(open(f"gpurun_out/prof_{sys.argv[1]}/run_kernel_trace.csv")))
+OUT = os.environ.get("GM2_OUT", "bench_out")  # the folder the tools/*.sh runs write to
+rows = list(csv.DictReader(open(OUT + f"/prof_{sys.argv[1]}/run_kernel_trace.csv")))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 gath = [i for i, r in enumerate(rows) if "k_gather" in r["Kernel_Name"] or "k_resident_rows" in r["Kernel_Name"]]
 lo, hi = gath[-2], gath[-1]

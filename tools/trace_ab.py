@@ -3,12 +3,14 @@
 import collections
 import csv
 import glob
+import os
 import re
 import sys
 
+OUT = os.environ.get("GM2_OUT", "bench_out")  # the folder the tools/*.sh runs write to
 tag = sys.argv[1]
 res = collections.defaultdict(lambda: collections.defaultdict(list))
-for d in sorted(glob.glob(f"gpurun_out/tab_{tag}_*_*/")):
+for d in sorted(glob.glob(OUT + f"/tab_{tag}_*_*/")):
     var = re.search(rf"tab_{tag}_(\d+)_\d+", d).group(1)
     for f in glob.glob(d + "**/*kernel_trace.csv", recursive=True):
         for r in csv.DictReader(open(f)):
