@@ -131,6 +131,17 @@ struct Layout {
   int64_t s3bits, s3ldb;
   int64_t adamscal;            // scalar block of a queued output-layer Adam update
   int64_t ridx;                // zero-copy rows: int32 [roundup(Bm, 256)] resident-matrix row per batch row
+  // GM2_BF16X3 (x3; otherwise empty regions): the split operands of the five G-wide GEMMs, bf16, with
+  // Gq = roundup(G, 256), Bq = roundup(Bm, 256). K-major splits interleave (hi | lo) per 32 columns,
+  // MN-major ones per 32 k-rows (launch_split_kmajor / launch_split_rows):
+  //   x3w0  [H][2 Gq]   encoder.0.weight, K-major        x3xd  [Bq][2 Gq]  the 0/1 input rows as (x | x)
+  //   x3w9k [Gq][2 H]   decoder.9.weight, K-major        x3x   [Bq][Gq]    the input rows once (dWe0's k-rows)
+  //   x3w9m [2 Gq][H]   decoder.9.weight, MN-major       x3a5k [Bq][2 H], x3a5m [2 Bq][H]  last activations
+  //   x3dlk [Bq][2 Gq], x3dlm [2 Bq][Gq]  dL             x3dy0 [2 Bq][H]   input layer's dY, MN-major
+  //   x3rows int32 [2 Bq]: the row table that names every row of x3x twice (dWe0's exact side)
+  bool x3 = false;
+  int64_t Gq = 0, Bq = 0;
+  int64_t x3w0, x3w9k, x3w9m, x3xd, x3x, x3a5k, x3a5m, x3dlk, x3dlm, x3dy0, x3rows;
 };
 
 #ifdef GM2_DEBUG
@@ -139,8 +150,11 @@ thread_local std::vector<std::pair<int64_t, int64_t>> t_regions;
 #endif
 
 Layout make_layout(const gm2_dims* gd, int prec) {
-  if (prec != GM2_F32 && prec != GM2_BF16) throw Gm2Error("bad precision %d", prec);
+  if (prec != GM2_F32 && prec != GM2_BF16 && prec != GM2_BF16X3) throw Gm2Error("bad precision %d", prec);
   Layout o;
+  // (GM2_BF16X3: the GM2_F32 layout, then the split operand buffers)
+  o.x3 = prec == GM2_BF16X3;
+  if (o.x3) prec = GM2_F32;
   o.d = make_dims(gd, prec == GM2_BF16 ? 2 * kTile : kTile);
   o.prec = prec;
   o.es = prec == GM2_F32 ? 4 : 2;
@@ -221,6 +235,20 @@ Layout make_layout(const gm2_dims* gd, int prec) {
   o.s3bits = take(split3 ? round_up(Bm, 2 * kTile) * o.s3ldb : 0);
   o.adamscal = take(GM2_NUM_SCALARS * 4);
   o.ridx = take(round_up(Bm, 2 * kTile) * 4);
+  o.Gq = round_up(d.G, 2 * kTile);
+  o.Bq = round_up(Bm, 2 * kTile);
+  const int64_t x3e = o.x3 ? 2 : 0, Gq = o.Gq, Bq = o.Bq;  // bytes per element of the split buffers
+  o.x3w0 = take(H * 2 * Gq * x3e);
+  o.x3w9k = take(Gq * 2 * H * x3e);
+  o.x3w9m = take(2 * Gq * H * x3e);
+  o.x3xd = take(Bq * 2 * Gq * x3e);
+  o.x3x = take(Bq * Gq * x3e);
+  o.x3a5k = take(Bq * 2 * H * x3e);
+  o.x3a5m = take(2 * Bq * H * x3e);
+  o.x3dlk = take(Bq * 2 * Gq * x3e);
+  o.x3dlm = take(2 * Bq * Gq * x3e);
+  o.x3dy0 = take(2 * Bq * H * x3e);
+  o.x3rows = take(2 * Bq * x3e * 2);
   o.total = cur;
   return o;
 }
@@ -244,6 +272,8 @@ struct Ctx {
   const uint32_t* xbres = nullptr;
   int64_t ld_xbres = 0;
   int64_t res_rows = 0;  // rows of the resident operands (their zero row included): bounds of ridx
+  bool x3 = false;       // GM2_BF16X3 with GM2_OPT_TRAIN_SPLIT on: the G-wide GEMMs as split-bf16 products
+  bf16_t* h(int64_t off) const { return (bf16_t*)(ws + off); }
   Ctx(const Layout& l, void* w, void* strm, WsState* state = nullptr)
       : lo(l), ws((char*)w), s((hipStream_t)strm), d(l.d), slab_off(l.slabs), slab_cap(l.slab_cap), xo(l.X),
         xbo(l.XB), st(state) {}
@@ -259,6 +289,7 @@ struct Ctx {
     c.xbres = xbres;
     c.ld_xbres = ld_xbres;
     c.res_rows = res_rows;
+    c.x3 = x3;
     return c;
   }
   T* t(int64_t off) const { return (T*)(ws + off); }
@@ -328,6 +359,7 @@ struct WsState {
                                     // GM2_OPT_SAMPLE_SPLIT = 0, preconditions): GM2_STAT_EXACT_DECODES
   const unsigned long long* decode_cum = nullptr;  // the gated decodes' cumulative device counters (DecodeCtl)
   const unsigned long long* decode_ovf = nullptr;  // their cumulative count of overflow-recomputed blocks
+  int64_t x3_split = 0, x3_exact = 0;  // GM2_TSTAT_*: G-wide GEMMs of a GM2_BF16X3 workspace run split / exact
   // the queued (not yet launched) output-layer update: launched by kick() beside the next training
   // call's hidden layers, or by join() on the joining stream
   struct QueuedAdam {
@@ -565,6 +597,81 @@ void linear_pre_bn(const Ctx<T>& c, const T* in, int64_t ldin, int Bp, const T* 
   launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)Bp * H, H, bias, B, H, Y, part, c.s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// GM2_BF16X3: which of the five G-wide GEMMs of a call run as split-bf16 products, with their
+// operands in the workspace's split buffers (Layout x3*). A GEMM splits when the hidden width tiles
+// by 256 and the bf16 plan of its doubled-K shape is a 256x256 one (the loss GEMM: when the 256x256
+// loss kernel fills the chip); the others run the exact-fp32 kernels as GM2_F32 does.
+//   enc0  Y = X . W0^T        plain K-tiles over (x | x) and (hi | lo): x.hi + x.lo (X is 0/1: exact)
+//   loss  logit^T = W9 . A5^T  three products, the exact BCE epilogue, fp32 dL
+//   dA5   = dL . W9           dL K-major, W9 MN-major, three products
+//   dW9   = dL^T . A5         both MN-major, three products, stored as decoder.9.weight's gradient
+//   dWe0  = dY0^T . X         dY0 MN-major split, X's k-rows named twice by a row table: hi.x + lo.x
+// ---------------------------------------------------------------------------------------------
+struct X3Plan {
+  bool enc0 = false, loss = false, da5 = false, dw9 = false, dwe0 = false;
+  GemmArgs<bf16_t> g_enc0{}, g_loss{}, g_da5{}, g_dw9{}, g_dwe0{};
+  int Bq = 0;
+  int count() const { return (int)enc0 + (int)loss + (int)da5 + (int)dw9 + (int)dwe0; }
+};
+
+// split-K slices of a split GEMM stored into C: the plan's, at most what the slab scratch holds
+inline int x3_store_splits(int64_t slab_cap, const GemmArgs<bf16_t>& g) {
+  const int S = plan_gemm<bf16_t>(g).splits;
+  const int64_t slab = round_up((int64_t)g.M * g.N, 4);
+  return (int64_t)S * slab > slab_cap ? (int)std::max<int64_t>(1, slab_cap / slab) : S;
+}
+
+template <typename T>
+X3Plan x3_plan(const Ctx<T>& c, int B) {
+  X3Plan p;
+  if (!c.x3 || sizeof(T) != 4) return p;
+  const Layout& l = c.lo;
+  const int H = (int)c.d.H, G = (int)c.d.G, Gq = (int)l.Gq, Bq = (int)round_up(B, 2 * kTile);
+  p.Bq = Bq;
+  if (H % (2 * kTile) || Bq > l.Bq) return p;
+  p.g_enc0 = GemmArgs<bf16_t>{c.h(l.x3xd), 2 * Gq, c.h(l.x3w0), 2 * Gq, B, H, 2 * Gq, Bq, H, 0};
+  p.g_loss = GemmArgs<bf16_t>{c.h(l.x3w9k), 2 * H, c.h(l.x3a5k), 2 * H, G, B, 2 * H, Gq, Bq, 0};
+  p.g_da5 = GemmArgs<bf16_t>{c.h(l.x3dlk), 2 * Gq, c.h(l.x3w9m), H, B, H, 2 * Gq, Bq, H, 0, 1, 0};
+  p.g_dw9 = GemmArgs<bf16_t>{c.h(l.x3dlm), Gq, c.h(l.x3a5m), H, G, H, 2 * Bq, Gq, H, 0, 0, 0};
+  p.g_dwe0 = GemmArgs<bf16_t>{c.h(l.x3dy0), H, c.h(l.x3x), Gq, H, G, 2 * Bq, H, Gq, 0, 0, 0};
+  p.g_dwe0.qrow = (const int32_t*)(c.ws + l.x3rows);
+  p.g_dwe0.idx_lim = Bq;
+  p.enc0 = gemm_x3_ok(p.g_enc0);
+  p.loss = gemm_recon_x3_ok(p.g_loss);
+  p.da5 = gemm_x3_ok(p.g_da5);
+  p.dw9 = gemm_x3_ok(p.g_dw9);
+  p.dwe0 = gemm_x3_ok(p.g_dwe0);
+  if (p.dwe0) {  // (its row table holds one slice's k-rows in LDS: the slices the launch will really take)
+    const int nkt = p.g_dwe0.K / 64, S = std::min(x3_store_splits(c.lo.slab_cap, p.g_dwe0), nkt);
+    p.dwe0 = (int)(round_up(nkt, S) / S) * 64 <= kMaxIdxRows;
+  }
+  return p;
+}
+
+// a split GEMM into the fp32 slab scratch (plain or, s3, three-product K-tiles). Returns #slabs.
+template <typename T>
+int x3_gemm_to_slabs(const Ctx<T>& c, const GemmArgs<bf16_t>& g, int64_t ldc, bool s3) {
+  const int64_t slab = (int64_t)g.Mp * ldc;
+  const int S = (int)std::min<int64_t>(plan_gemm<bf16_t>(g).splits, c.slab_cap / std::max<int64_t>(slab, 1));
+  if (S < 1) throw Gm2Error("slab capacity exceeded");
+  if (s3) return launch_gemm_store_x3(g, S, c.f(c.slab_off), ldc, slab, nullptr, c.s);
+  return launch_gemm_store<bf16_t>(g, S, c.f(c.slab_off), nullptr, 0, ldc, slab, nullptr, c.s);
+}
+
+// a split GEMM into C (fp32 [M][ldc]); short-grid plans go through split-K slabs like gemm_to
+template <typename T>
+void x3_gemm_to(const Ctx<T>& c, const GemmArgs<bf16_t>& g, float* C, int64_t ldc) {
+  int S = x3_store_splits(c.slab_cap, g);
+  const int64_t slab = round_up((int64_t)g.M * g.N, 4);
+  if (S <= 1) {
+    launch_gemm_store_x3(g, 1, C, ldc, 0, nullptr, c.s);
+    return;
+  }
+  S = launch_gemm_store_x3(g, S, c.f(c.slab_off), g.N, slab, nullptr, c.s);
+  launch_slab_sum(c.f(c.slab_off), S, slab, g.M, g.N, C, nullptr, g.M, ldc, c.s);
+}
+
 // Tensor tables. kind 0: the 9 Linear weights with their natural-layout shadow (tile0 counts
 // 64x64 tiles; fp32 -> shadow sync). kind 1: all 30 parameters in reference order, weights with
 // their shadow (tile0 counts 4096-element blocks; fused Adam writes the shadow).
@@ -667,6 +774,8 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   int64_t ldin = c.ridx ? c.ld_xres : d.Gp;
   int Kin = (int)d.Gp;
   const int64_t shadow_in[6] = {l.sE0, l.sE1, l.sE2, l.sD0, l.sD1, l.sD2};
+  const X3Plan xp = x3_plan<T>(c, B);
+  const int64_t Gq = l.Gq;
   for (int i = 0; i < 6; ++i) {
     if (i == 3) {
       const int S = gemm_to_slabs<T>(c, c.t(l.A[2]), H, Bp, c.t(l.sHD), H, (int)d.L2r, B, 2 * L, H, 2 * L);
@@ -676,8 +785,21 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
       ldin = d.Lr;
       Kin = (int)d.Lp;
     }
-    linear_pre_bn<T>(c, in, ldin, Bp, c.t(shadow_in[i]), i == 3 ? d.Lr : Kin, B, H, Kin, prm + d.off[kBlk[i][1]],
-                     c.f(l.Y[i]), c.f(l.bnpart), train != 0, i == 0 ? c.ridx : nullptr);
+    if (i == 0 && xp.enc0) {
+      // bf16x3 input layer: X as (x | x) (and once more plain, for the backward's dWe0), the fp32
+      // weight shadow split per call (an Adam step or a shadow sync in between is always seen)
+      launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1,
+                          with_grad && xp.dwe0 ? c.h(l.x3x) : nullptr, Gq, c.s);
+      launch_split_kmajor(c.f(l.sE0), d.Gp, H, (int)d.G, H, (int)Gq, c.h(l.x3w0), 2 * Gq, 0, nullptr, 0, c.s);
+      const int S = x3_gemm_to_slabs<T>(c, xp.g_enc0, H, false);
+      launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)xp.Bq * H, H, prm + d.off[kBlk[i][1]], B, H, c.f(l.Y[i]),
+                            c.f(l.bnpart), c.s);
+    } else {
+      if (i == 0 && with_grad && xp.dwe0)  // (the exact input layer beside a split dWe0: X in bf16 all the same)
+        launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1, c.h(l.x3x), Gq, c.s);
+      linear_pre_bn<T>(c, in, ldin, Bp, c.t(shadow_in[i]), i == 3 ? d.Lr : Kin, B, H, Kin, prm + d.off[kBlk[i][1]],
+                       c.f(l.Y[i]), c.f(l.bnpart), train != 0, i == 0 ? c.ridx : nullptr);
+    }
     // a queued output-layer Adam update of the previous step starts here, beside the hidden layers
     // (HBM-bound next to latency-bound small GEMMs; the gather and the input-layer GEMM before this
     // point leave it nothing: one is HBM-bound too, the other holds every CU's registers)
@@ -706,7 +828,12 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   if (c.st) c.st->join(c.s);
   GemmArgs<T> g{c.t(l.sD3), H, c.t(l.A[5]), H, (int)d.G, B, H, (int)d.Gp, Bp, 0};
   if (c.ridx) g.idx_lim = c.res_rows;
-  if (c.ridx)
+  if (xp.loss) {
+    launch_split_kmajor(c.f(l.sD3), H, (int)d.G, H, (int)Gq, H, c.h(l.x3w9k), 2 * H, 0, nullptr, 0, c.s);
+    launch_split_kmajor(c.f(l.A[5]), H, B, H, xp.Bq, H, c.h(l.x3a5k), 2 * H, 0, nullptr, 0, c.s);
+    launch_gemm_recon_loss_x3(xp.g_loss, prm + d.off[D9B], (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, with_grad, scal,
+                              c.f(l.dL), d.Gp, (int)d.Gp, Bp, c.f(l.losspart), c.f(l.colpart), d.Gp, c.s);
+  } else if (c.ridx)
     launch_gemm_recon_loss<T>(g, prm + d.off[D9B], c.xbres, c.ld_xbres, with_grad, scal, c.t(l.dL), d.Gp,
                               c.f(l.losspart), c.f(l.colpart), d.Gp, c.s, c.ridx);
   else
@@ -715,7 +842,7 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   int na_ok = 0, na_n = 0;
   if (norm_hdr) {  // the training call: record whether its backward takes the clip statistics
     const BigGrads<T> bg = big_grads<T>(c, Bp);
-    na_ok = bg.direct ? 1 : 0;
+    na_ok = bg.direct && !xp.dw9 && !xp.dwe0 ? 1 : 0;  // (the split weight gradients take no clip statistics)
     na_n = bg.n9 + bg.n0;
   }
   // 4) loss slot sums + the output bias's gradient (column sums of dL): nothing in the backward
@@ -723,7 +850,8 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   // puts it on the side stream behind its first fork (off the critical path, one launch and its
   // gap fewer on the caller's stream)
   const float* lpart = c.f(l.losspart);
-  const int nlp = gemm_recon_grid_blocks<T>(g), nkp = Bp / kReparamRows, rt = gemm_recon_row_tiles<T>(g);
+  const int nlp = xp.loss ? (int)(Gq / 256) * (xp.Bq / 256) : gemm_recon_grid_blocks<T>(g);
+  const int nkp = Bp / kReparamRows, rt = xp.loss ? xp.Bq / 256 : gemm_recon_row_tiles<T>(g);
   const float *kpart = c.f(l.klpart), *cpart = c.f(l.colpart);
   const int64_t Gp = d.Gp, G = d.G;
   float* bgrad = with_grad ? grads + d.off[D9B] : nullptr;
@@ -797,6 +925,8 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
   // (Forking it last instead, beside the input-layer dWe0 GEMM, measured the same step time on one
   // GPU; first keeps gradient bucket 0 early for the data-parallel exchange.)
   const BigGrads<T> bg = big_grads<T>(c, Bp);
+  const X3Plan xp = x3_plan<T>(c, B);
+  const int Gq = (int)l.Gq;
   double* nasq = (double*)(c.ws + l.nasq);
   // the forward's deferred tail launch (loss sums, output bias gradient): behind the first fork
   auto tail_on = [&](hipStream_t s) {
@@ -829,7 +959,11 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     const bool direct9 = plan_gemm<T>(g9).splits == 1;
     fork();
     tail_on(s9);
-    if (direct9) {
+    if (xp.dw9) {  // bf16x3: dL and A5 as MN-major splits (k = the batch row), both made on this stream
+      launch_split_rows(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlm), Gq, s9);
+      launch_split_rows(c.f(l.A[5]), H, B, H, xp.Bq, H, c.h(l.x3a5m), H, s9);
+      x3_gemm_to<T>(w, xp.g_dw9, gr + d.off[D9W], H);
+    } else if (direct9) {
       // (A5^T here on the side stream; on the main stream before the fork measured ~35 us/step
       // slower, profiles/r02_a5t_placement_ab.txt)
       launch_transpose<T>(c.t(l.A[5]), H, Bp, H, c.t(l.AT5), Bp, s9);
@@ -861,11 +995,18 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     have_part = launch_gemm_bn<T>(g, c.f(c.slab_off), H, nullptr, bn, c.s);
     return have_part ? 1 : gemm_to_slabs<T>(c, dY, lddy, Bp, W, ldw, H, B, H, K, H, 1, 0);
   };
-  int S = dx_pre_bn(c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
+  int S;
+  if (xp.da5) {  // bf16x3: dL K-major and W9 MN-major (its natural [G][H] rows interleaved), to slabs
+    launch_split_kmajor(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlk), 2 * (int64_t)Gq, 0, nullptr, 0, c.s);
+    launch_split_rows(c.f(l.sD3), H, G, H, Gq, H, c.h(l.x3w9m), H, c.s);
+    S = x3_gemm_to_slabs<T>(c, xp.g_da5, H, true);
+  } else {
+    S = dx_pre_bn(c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
+  }
   chain_mark();
   const int64_t shadow_w[6] = {l.sE0, l.sE1, l.sE2, l.sD0, l.sD1, l.sD2};
   for (int i = 5; i >= 0; --i) {
-    const int64_t slab = (int64_t)Bp * H;
+    const int64_t slab = (int64_t)(i == 5 && xp.da5 ? xp.Bq : Bp) * H;
     const bool sum = S > 1;
     if (!have_part)
       launch_bn_bwd_partial(c.f(c.slab_off), S, slab, c.f(l.Y[i]), H, c.f(l.save[i]), prm + d.off[kBlk[i][2]],
@@ -893,12 +1034,18 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     if (i == 0) {  // input layer: weight gradient only (on the main stream: nothing left to overlap)
       dw9_launch();  // (a dw9_at past the chain's end: here, beside dWe0)
       // dWe0[h][g] = sum_b dY0^T[h][b] X[b][g]: dY0^T (K-major copy) x X (MN-major)
-      if (!dyt) launch_transpose<T>(dY, H, Bp, H, c.t(l.dYT0), Bp, c.s);
+      if (!dyt && !xp.dwe0) launch_transpose<T>(dY, H, Bp, H, c.t(l.dYT0), Bp, c.s);
       // bucket 1 (every hidden-layer weight gradient) is final when the side stream's queue so far
       // is; dWe0 starts without waiting for it (the join follows the dWe0 launch: the side stream's
       // last small GEMM / column sums run beside dWe0's first tiles instead of before them)
       if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[1], w.s));
-      if (input_chunked(bg, H)) {  // four row-quarter launches, bucket 2 + q final after launch q
+      if (xp.dwe0) {  // bf16x3: dY0 as an MN-major split, X's rows (exact in bf16) named twice by the row table
+        launch_split_rows(c.f(l.dY[0]), H, B, H, xp.Bq, H, c.h(l.x3dy0), H, c.s);
+        launch_dup_rows((int32_t*)(c.ws + l.x3rows), 2 * xp.Bq, c.s);
+        x3_gemm_to<T>(c, xp.g_dwe0, gr + d.off[E0W], G);
+        if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2], c.s));
+        for (int q = 0; q < 4; ++q) st.bucket_ev[2 + q] = 2;
+      } else if (input_chunked(bg, H)) {  // four row-quarter launches, bucket 2 + q final after launch q
         for (int q = 0; q < 4; ++q) {
           GemmArgs<T> gq = bg.g0;
           const int r0 = (int)input_quarter_row(d, q);
@@ -1180,6 +1327,12 @@ void run_train(const Layout& lo, const gm2_batch* b, const float* prm, float* gr
     return;
   }
   Ctx<T> c(lo, ws, strm, &st);
+  c.x3 = lo.x3 && st.opt.train_split != 0;
+  if (lo.x3) {  // GM2_TSTAT_*: this call's five G-wide GEMMs
+    const int n = x3_plan<T>(c, (int)b->n).count();
+    st.x3_split += n;
+    st.x3_exact += 5 - n;
+  }
   if (zero_copy_ok<T>(c, b)) {  // the resident matrix's rows in place: no gather, no staging
     c.ridx = (const int32_t*)((char*)ws + lo.ridx);
     c.xres = (const T*)b->resident;
@@ -1283,7 +1436,7 @@ int gm2_workspace_init(const gm2_dims* d, int prec, void* ws, size_t ws_bytes, v
 int gm2_sync_shadows(const gm2_dims* d, int prec, const float* params, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {
     const Layout lo = make_layout(d, prec);
-    if (prec == GM2_F32) {
+    if (lo.prec == GM2_F32) {
       Ctx<float> c(lo, ws, stream, &st);
       launch_shadow_sync<float>(make_table(c), params, c.s);
     } else {
@@ -1334,7 +1487,7 @@ int gm2_train_fwd_bwd(const gm2_dims* d, int prec, const gm2_batch* batch, const
                       float* bn_running, const float* scalars, double* loss, void* ws, void* stream) {
   return with_ws(ws, [&](WsState& st) {
     const Layout lo = make_layout(d, prec);
-    if (prec == GM2_F32) run_train<float>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
+    if (lo.prec == GM2_F32) run_train<float>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
     else run_train<bf16_t>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
   });
 }
@@ -1375,7 +1528,7 @@ int gm2_adam_step(const gm2_dims* d, int prec, float* params, const float* grads
       launch_adam_fused<T>(table_range(all, 0, all.n - 2), grads, params, m, v, scalars, clip, c.s, 0, qs);
       WsState::QueuedAdam& q = st.qadam;
       q.queued = true;
-      q.prec = prec;
+      q.prec = lo.prec;
       q.tt = table_range(all, all.n - 2, all.n);
       q.g = grads;
       q.p = params;
@@ -1384,7 +1537,7 @@ int gm2_adam_step(const gm2_dims* d, int prec, float* params, const float* grads
       q.scal = qs;
       q.clip = clip;
     };
-    if (prec == GM2_F32) run(float{});
+    if (lo.prec == GM2_F32) run(float{});
     else run(bf16_t{});
   });
 }
@@ -1395,8 +1548,14 @@ int gm2_eval_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const 
     const Layout lo = make_layout(d, prec);
     drop_stage(st, (hipStream_t)stream);  // these write input slot 0
     float* bn = const_cast<float*>(bn_running);  // eval mode never writes running stats
-    if (prec == GM2_F32) {
+    if (lo.prec == GM2_F32) {
       Ctx<float> c(lo, ws, stream, &st);
+      c.x3 = lo.x3 && st.opt.train_split != 0;
+      if (lo.x3) {  // GM2_TSTAT_*: the input layer and the output layer + loss
+        const X3Plan xp = x3_plan<float>(c, (int)batch->n);
+        st.x3_split += (int)xp.enc0 + (int)xp.loss;
+        st.x3_exact += 2 - ((int)xp.enc0 + (int)xp.loss);
+      }
       forward<float>(c, batch, params, bn, 0, 0, scalars, loss, nullptr);
     } else {
       Ctx<bf16_t> c(lo, ws, stream, &st);
@@ -1475,7 +1634,7 @@ int gm2_recon_counts(const gm2_dims* d, int prec, const gm2_batch* batch, const 
       Ctx<T> c(lo, ws, stream, &st);
       forward<T>(c, batch, params, bn, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, counts, threshold);
     };
-    if (prec == GM2_F32) run(float{});
+    if (lo.prec == GM2_F32) run(float{});
     else run(bf16_t{});
   });
 }
@@ -1517,7 +1676,7 @@ int gm2_encode(const gm2_dims* d, int prec, const gm2_batch* batch, const float*
       if (logvar)
         HIP_OK(hipMemcpy2DAsync(logvar, L * 4, c.f(lo.HD) + L, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
     };
-    if (prec == GM2_F32) run(float{});
+    if (lo.prec == GM2_F32) run(float{});
     else run(bf16_t{});
   });
 }
@@ -1540,9 +1699,36 @@ int gm2_gemm(int prec, int pk, int qk, const void* P, int64_t ldp, const void* Q
         launch_colsum(slab_ws, S, M * ldc, M * ldc, C, nullptr, 0, (hipStream_t)stream);
       }
     };
-    if (prec == GM2_F32) run(float{});
-    else if (prec == GM2_BF16) run(bf16_t{});
-    else throw Gm2Error("bad precision");
+    if (prec == GM2_F32) {
+      run(float{});
+    } else if (prec == GM2_BF16) {
+      run(bf16_t{});
+    } else if (prec == GM2_BF16X3) {  // operands from gm2_split_operand, K the real K
+      if (K <= 0 || K % 32) throw Gm2Error("gemm (bf16x3): K %lld must be a positive multiple of 32", (long long)K);
+      GemmArgs<bf16_t> g{(const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, (int)M, (int)N, (int)(2 * K),
+                         (int)round_up(M, 2 * kTile), (int)round_up(N, 2 * kTile), 0, pk ? 1 : 0, qk ? 1 : 0};
+      if (splits < 0) splits = plan_gemm(g).splits;
+      if (splits == 0 || splits == 1) {
+        launch_gemm_store_x3(g, 1, C, ldc, 0, nullptr, (hipStream_t)stream);
+      } else {
+        if (!slab_ws) throw Gm2Error("gemm: split-K needs slab_ws");
+        const int S = launch_gemm_store_x3(g, splits, slab_ws, ldc, (int64_t)M * ldc, nullptr, (hipStream_t)stream);
+        launch_colsum(slab_ws, S, M * ldc, M * ldc, C, nullptr, 0, (hipStream_t)stream);
+      }
+    } else {
+      throw Gm2Error("bad precision");
+    }
+  });
+}
+
+int gm2_split_operand(const float* X, int64_t ldx, int64_t rows, int64_t K, int kmajor, uint16_t* out, int64_t ldo,
+                      void* stream) {
+  return guarded([&] {
+    if (!X || !out || rows <= 0 || K <= 0 || K % 32 || rows > INT32_MAX - 256 || K > INT32_MAX / 2)
+      throw Gm2Error("split operand: rows %lld, K %lld (a positive multiple of 32)", (long long)rows, (long long)K);
+    const int rp = (int)round_up(rows, 2 * kTile);
+    if (kmajor) launch_split_kmajor(X, ldx, (int)rows, (int)K, rp, (int)K, out, ldo, 0, nullptr, 0, (hipStream_t)stream);
+    else launch_split_trans(X, ldx, (int)rows, (int)K, rp, out, ldo, (hipStream_t)stream);
   });
 }
 
@@ -1562,7 +1748,7 @@ int gm2_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const float
       if (logvar)
         HIP_OK(hipMemcpy2DAsync(logvar, L * 4, c.f(lo.HD) + L, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
     };
-    if (prec == GM2_F32) run(float{});
+    if (lo.prec == GM2_F32) run(float{});
     else run(bf16_t{});
   });
 }
@@ -1588,7 +1774,7 @@ int gm2_backward_outputs(const gm2_dims* d, int prec, const gm2_batch* batch, co
       HIP_OK(hipMemsetAsync(scal0, 0, GM2_NUM_SCALARS * 4, c.s));
       backward<T>(c, batch, params, grads, scal0, dmu, dlogvar, train);
     };
-    if (prec == GM2_F32) run(float{});
+    if (lo.prec == GM2_F32) run(float{});
     else run(bf16_t{});
   });
 }
@@ -1690,6 +1876,8 @@ int gm2_workspace_stat(void* ws, int key, int64_t* value) {
         }
         break;
       }
+      case GM2_TSTAT_SPLIT_GEMMS: *value = st.x3_split; break;
+      case GM2_TSTAT_EXACT_GEMMS: *value = st.x3_exact; break;
       default: throw Gm2Error("unknown statistic %d", key);
     }
   });
@@ -1747,7 +1935,8 @@ int gm2_debug_check_layout(const gm2_dims* d, int precision, int64_t* n_regions,
                              o.slabs, o.side_slabs, o.DA, o.dH, o.AT5, o.dYT0, o.bnpart, o.colpart, o.losspart,
                              o.klpart, o.gradpart, o.colbwd, o.nahdr, o.nasq, o.clip, o.scal0, o.X1, o.XB1, o.syncb,
                              o.s3a, o.s3w, o.s3rn, o.s3cn, o.s3ctl, o.s3band, o.s3tlist, o.s3tcount, o.s3a1, o.s3w1,
-                             o.s3ovf, o.s3bits, o.adamscal, o.ridx};
+                             o.s3ovf, o.s3bits, o.adamscal, o.ridx, o.x3w0, o.x3w9k, o.x3w9m, o.x3xd, o.x3x, o.x3a5k,
+                             o.x3a5m, o.x3dlk, o.x3dlm, o.x3dy0, o.x3rows};
     auto known = [&](int64_t off) {
       for (const auto& x : r)
         if (x.first == off) return true;

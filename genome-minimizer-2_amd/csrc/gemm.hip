@@ -589,7 +589,7 @@ __device__ __forceinline__ double sq4(float a, float b, float c, float d) {
   return ((double)a * a + (double)b * b) + ((double)c * c + (double)d * d);
 }
 
-template <class C, typename T, bool AK, bool BK, bool PP, int IDX, int EPI>
+template <class C, typename T, bool AK, bool BK, bool PP, int IDX, int EPI, bool S3>
 __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g, float* __restrict__ C0,
                                            float* __restrict__ C1, int msplit, int64_t ldc, int64_t slab,
                                            const float* __restrict__ bias, const StoreEpi& bn, char* smem);
@@ -602,7 +602,9 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
 // 1 = plain fp32 store (split-K slabs or one pass, rows aligned or not, optional per-tile sums of
 // squares), 2 = the transposed store straight from the accumulators (+ sums of squares), 3 = the
 // transposed store through the LDS image (+ sums of squares)
-template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0>
+// S3 (PP only; GM2_BF16X3 training): both operands in the split layout of k_split_kmajor / k_split_rows
+// (g.K = twice the real K) and the main loop in its hi.hi + hi.lo + lo.hi form
+template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0, bool S3 = false>
 __global__ __launch_bounds__(C::NT, C::MINW) void k_gemm_store(GemmArgs<T> g, float* __restrict__ C0, float* __restrict__ C1,
                                                     int msplit, int64_t ldc, int64_t slab,
                                                     const float* __restrict__ bias, StoreEpi bn) {
@@ -610,7 +612,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void k_gemm_store(GemmArgs<T> g, fl
   GM2_STAMP(0);
   const int tm = g.Mp / C::BM, tn = g.Np / C::BN;
   if (bn.ntiles == 0) {  // one tile per workgroup
-    store_tile<C, T, AK, BK, PP, IDX, EPI>(tile_of<C>(tm, tn), g, C0, C1, msplit, ldc, slab, bias, bn, smem);
+    store_tile<C, T, AK, BK, PP, IDX, EPI, S3>(tile_of<C>(tm, tn), g, C0, C1, msplit, ldc, slab, bias, bn, smem);
     return;
   }
   // capped grid (one K pass): workgroup wg takes logical tiles wg, wg + grid, ... (every wave of
@@ -618,12 +620,12 @@ __global__ __launch_bounds__(C::NT, C::MINW) void k_gemm_store(GemmArgs<T> g, fl
   const int ntile = tm * tn;
   for (int t = xcd_wg(); t < bn.ntiles; t += gridDim.x) {
     __syncthreads();
-    store_tile<C, T, AK, BK, PP, IDX, EPI>(tile_at<C>(t % ntile, tm, tn, t / ntile), g, C0, C1, msplit, ldc, slab, bias,
-                                      bn, smem);
+    store_tile<C, T, AK, BK, PP, IDX, EPI, S3>(tile_at<C>(t % ntile, tm, tn, t / ntile), g, C0, C1, msplit, ldc, slab,
+                                               bias, bn, smem);
   }
 }
 
-template <class C, typename T, bool AK, bool BK, bool PP, int IDX, int EPI>
+template <class C, typename T, bool AK, bool BK, bool PP, int IDX, int EPI, bool S3>
 __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g, float* __restrict__ C0,
                                            float* __restrict__ C1, int msplit, int64_t ldc, int64_t slab,
                                            const float* __restrict__ bias_in, const StoreEpi& bn, char* smem) {
@@ -651,9 +653,9 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
       }
       __syncthreads();
     }
-    mainloop_pp<AK, BK, IDX>(g.P, g.ldp, g.Q, g.ldq, tl.m0, tl.n0, kbeg, nk, smem, acc, sidx);
+    mainloop_pp<AK, BK, IDX, S3>(g.P, g.ldp, g.Q, g.ldq, tl.m0, tl.n0, kbeg, nk, smem, acc, sidx);
   } else {
-    static_assert(IDX == 0, "zero-copy rows: ping-pong main loop only");
+    static_assert(IDX == 0 && !S3, "zero-copy rows, split operands: ping-pong main loop only");
     mainloop<C, T, AK, BK>(g.P, g.ldp, g.Q, g.ldq, tl.m0, tl.n0, kbeg, nk, smem, acc);
   }
   GM2_STAMP(2);
@@ -1212,6 +1214,153 @@ constexpr int recon_lds_bytes() {
   constexpr int img = std::max<int>(C::LDS, C::BN * (C::BM + 8) * (int)sizeof(T));
   constexpr int rg = C::NT / (C::BM / (16 / (int)sizeof(T)));
   return img + (rg * C::BM + 64 + C::BM + C::BN) * 4;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Epilogue 2 for GM2_BF16X3: the loss epilogue in its exact (non-FAST) form behind the 256x256
+// ping-pong main loop in its S3 form, over W9 and A5 in the split layout (g.K = 2H). dL, colpart and
+// the loss partials are fp32 as in the GM2_F32 kernel. The exact element math on 128 accumulator
+// registers per lane does not fit the 256 a wave of this tile has (it spilled 334), so the math
+// moves out of the fragment layout: the raw logits go through an LDS image, and the pass that
+// stores dL computes bias, sigmoid, BCE and dl for the 4 genes x 16 strains each thread owns, in a
+// rolled loop. A 256-strain fp32 image would not fit the LDS, so the image holds 128 strains and is
+// filled twice, each time from half of every wave's strain fragments (every wave works in both).
+// The tile may reach past what the fp32 workspace allocates (its gene axis is padded to 128, its
+// rows to the 128-padded batch): elements at genes >= gcols or strains >= drows are not touched.
+// dL is zero outside the valid G x B box; padded genes and strains add nothing to the sums.
+// ---------------------------------------------------------------------------------------------
+constexpr int kX3ImgRows = 128;
+constexpr int recon_x3_img_bytes() { return std::max<int>(Big::LDS, kX3ImgRows * (Big::BM + 8) * 4); }
+constexpr int recon_x3_lds_bytes() { return recon_x3_img_bytes() + (8 * Big::BM + 64 + Big::BM) * 4; }
+
+template <bool GRAD>
+__device__ __forceinline__ void recon_loss_tile_x3(const TileXY tl, const GemmArgs<bf16_t>& g,
+                                                   const float* __restrict__ bias, const uint32_t* __restrict__ xbits,
+                                                   int64_t ldxb, const float* __restrict__ scal, float* __restrict__ dL,
+                                                   int64_t ldd, int gcols, int drows, float* __restrict__ loss_part,
+                                                   float* __restrict__ colpart, int64_t ldcol, char* smem) {
+  using C = Big;
+  constexpr int PR = C::BM + 8;
+  constexpr int CPR = C::BM / 4;   // 16-byte chunks per image row
+  constexpr int RG = C::NT / CPR;  // row groups of the element pass
+  static_assert(RG == 8 && C::FN == 4 && C::WTN == 64 && C::FM == 8, "bf16x3 loss tile shape");
+  float* colred = (float*)(smem + recon_x3_img_bytes());  // [RG][BM]
+  float* red = colred + RG * C::BM;                       // [2][32]
+  float* bias_s = red + 64;                               // [BM]
+  GM2_DBG(tl.m0 + C::BM <= g.Mp && tl.n0 + C::BN <= g.Np, kDbgTile);
+  f32x4 acc[C::FM][C::FN];
+  mainloop_pp<true, true, 0, true>(g.P, g.ldp, g.Q, g.ldq, tl.m0, tl.n0, 0, g.K / 64, smem, acc);
+  {
+    // the tile's bias slice, filled after the main loop (read behind the first barrier below). The
+    // index is made opaque so that its LDS address is formed here and not kept in a register -- a
+    // spilled one -- across the main loop of every tile of a capped grid
+    int i = threadIdx.x;
+    asm volatile("" : "+v"(i));
+    if (i < C::BM) bias_s[i] = tl.m0 + i < g.M ? bias[tl.m0 + i] : 0.f;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wm = wid / C::WGN, wn = wid % C::WGN;
+  const int q = lane >> 4, c = lane & 15;
+  const float wgam = scal[kScalWGamma];
+  float* img = (float*)smem;  // [128 strains][BM genes + 8] raw logits
+  // the element pass: this thread's 4 genes (chunk cch) of image rows r0, r0 + RG, ...
+  const int cch = threadIdx.x % CPR, r0 = threadIdx.x / CPR;
+  const int gene0 = tl.m0 + cch * 4;
+  const bool col_ok = gene0 < gcols;
+  const uint32_t* xcol = xbits + (gene0 >> 5);
+  const int xsh = gene0 & 31;
+  float bce = 0.f, psum = 0.f;
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    // this half's logits: strain fragments 2h, 2h + 1 of every wave -> image row wn * 32 + (ni & 1) * 16 + c
+#pragma unroll
+    for (int nl = 0; nl < 2; ++nl) {
+      float* irow = img + (wn * 32 + nl * 16 + c) * PR + wm * C::WTM + 4 * q;
+#pragma unroll
+      for (int mi = 0; mi < C::FM; ++mi) *(f32x4*)(irow + mi * 16) = acc[mi][2 * h + nl];
+    }
+    __syncthreads();
+    if (col_ok) {
+      const float4 b4 = *(const float4*)(bias_s + cch * 4);
+      const float bs[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll 1
+      for (int r = r0; r < kX3ImgRows; r += RG) {
+        const int strain = tl.n0 + (r >> 5) * 64 + h * 32 + (r & 31);
+        if (strain >= drows) continue;
+        const bool sok = strain < g.N;
+        float dl4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (sok) {
+          const float4 v4 = *(const float4*)(img + r * PR + cch * 4);
+          const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+          const uint32_t xw = xcol[(int64_t)strain * ldxb] >> xsh;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (gene0 + j >= g.M) continue;
+            // (the reference's formula order, as the GM2_F32 kernel's exact path)
+            const bool x = (xw >> j) & 1u;
+            const float l = v[j] + bs[j];
+            const float p = 1.0f / (1.0f + expf(-l));
+            bce += x ? -fmaxf(logf(p), -100.f) : -fmaxf(log1pf(-p), -100.f);
+            psum += p;
+            if constexpr (GRAD) {
+              const float omp = 1.0f - p;
+              const float dp = (p - (x ? 1.0f : 0.0f)) / fmaxf(omp * p, 1e-12f) + wgam;
+              dl4[j] = dp * omp * p;
+              cs[j] += dl4[j];
+            }
+          }
+        }
+        if constexpr (GRAD)
+          __builtin_nontemporal_store(f32x4{dl4[0], dl4[1], dl4[2], dl4[3]},
+                                      (f32x4*)(dL + (int64_t)strain * ldd + gene0));
+      }
+    }
+    __syncthreads();  // (the image is rewritten by the second half)
+  }
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) colred[r0 * C::BM + cch * 4 + e] = cs[e];
+  }
+  bce = wave_sum(bce);
+  psum = wave_sum(psum);
+  if (lane == 0) { red[wid] = bce; red[32 + wid] = psum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f;
+    for (int w = 0; w < C::NT / 64; ++w) { a += red[w]; b += red[32 + w]; }
+    loss_part[tl.t * 2 + 0] = a;
+    loss_part[tl.t * 2 + 1] = b;
+  }
+  if constexpr (GRAD) {
+    for (int cc = threadIdx.x; cc < C::BM; cc += C::NT) {
+      const int gg = tl.m0 + cc;
+      float v = 0.f;
+#pragma unroll
+      for (int w = 0; w < RG; ++w) v += colred[w * C::BM + cc];
+      if (gg < g.M) colpart[(int64_t)(tl.n0 / C::BN) * ldcol + gg] = v;
+    }
+  }
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(Big::NT) void k_gemm_recon_loss_x3(GemmArgs<bf16_t> g, const float* __restrict__ bias,
+                                                                const uint32_t* __restrict__ xbits, int64_t ldxb,
+                                                                int ntiles, const float* __restrict__ scal,
+                                                                float* __restrict__ dL, int64_t ldd, int gcols, int drows,
+                                                                float* __restrict__ loss_part,
+                                                                float* __restrict__ colpart, int64_t ldcol) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tm = g.Mp / Big::BM, tn = g.Np / Big::BN;
+  if (ntiles == 0) {
+    recon_loss_tile_x3<GRAD>(tile_of<Big>(tm, tn), g, bias, xbits, ldxb, scal, dL, ldd, gcols, drows, loss_part, colpart,
+                             ldcol, smem);
+    return;
+  }
+  for (int t = xcd_wg(); t < ntiles; t += gridDim.x) {
+    __syncthreads();
+    recon_loss_tile_x3<GRAD>(tile_at<Big>(t, tm, tn, 0), g, bias, xbits, ldxb, scal, dL, ldd, gcols, drows, loss_part,
+                             colpart, ldcol, smem);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1810,7 +1959,7 @@ static int device_cus() {
   return cus[dev] = std::max(n, 1);
 }
 
-template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0>
+template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0, bool S3 = false>
 static void store_launch_k(const GemmArgs<T>& a, int tiles, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
                            const float* bias, const StoreEpi& bn, hipStream_t s) {
   // (zero-copy rows: the index table after the staging ring -- a tile's rows, or a split's k-rows)
@@ -1819,7 +1968,7 @@ static void store_launch_k(const GemmArgs<T>& a, int tiles, float* C0, float* C1
   const int lds = C::LDS + (IDX == 1 ? C::BM * 4 : IDX == 2 ? a.k_per_split * 4 : 0);
   if (lds > 160 * 1024) throw Gm2Error("gemm: %d bytes of LDS", lds);
   if (IDX == 2 && a.k_per_split > kMaxIdxRows) throw Gm2Error("zero-copy rows: %d k-rows per split", a.k_per_split);
-  ensure_lds_attr((const void*)k_gemm_store<C, T, AK, BK, PP, IDX, EPI>, C::LDS + table_max);
+  ensure_lds_attr((const void*)k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>, C::LDS + table_max);
   int grid = tiles;
   StoreEpi ep = bn;
   if (bn.ntiles) {  // capped grid: the same number of rounds on fewer CUs
@@ -1827,7 +1976,7 @@ static void store_launch_k(const GemmArgs<T>& a, int tiles, float* C0, float* C1
     grid = (tiles + rounds - 1) / rounds;
     ep.ntiles = grid < tiles ? tiles : 0;
   }
-  hipLaunchKernelGGL((k_gemm_store<C, T, AK, BK, PP, IDX, EPI>), dim3(grid), dim3(C::NT), lds, s, a, C0, C1 ? C1 : C0,
+  hipLaunchKernelGGL((k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>), dim3(grid), dim3(C::NT), lds, s, a, C0, C1 ? C1 : C0,
                      C1 ? msplit : (1 << 30), ldc, slab, bias, ep);
 }
 
@@ -2048,6 +2197,73 @@ void launch_gemm_recon_loss(const GemmArgs<T>& g, const float* bias, const uint3
     }
   }
   if (!done) recon_impl<Small, T>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
+  GM2_CHECK_LAUNCH();
+}
+
+// ---- GM2_BF16X3: the split-operand GEMMs (gm2_kernels.hpp) ----
+bool gemm_x3_ok(const GemmArgs<bf16_t>& g) {
+  if (!pp_enabled() || g.Mp % 256 || g.Np % 256 || g.K % 64 || plan_gemm<bf16_t>(g).tile != 256) return false;
+  if (!g.qrow) return true;
+  const int nkt = g.K / 64, splits = std::max(1, std::min(plan_gemm<bf16_t>(g).splits, nkt));
+  return (int)(round_up(nkt, splits) / splits) * 64 <= kMaxIdxRows;
+}
+
+int launch_gemm_store_x3(const GemmArgs<bf16_t>& g, int splits, float* C, int64_t ldc, int64_t slab, double* sq,
+                         hipStream_t s) {
+  if (!pp_enabled()) throw Gm2Error("bf16x3 GEMM needs the ping-pong main loop (GM2_OPT_GEMM_PP)");
+  check_gemm(g, 256);
+  if (g.prow) throw Gm2Error("bf16x3 GEMM: P row table not instantiated");
+  GemmArgs<bf16_t> a = g;
+  const int nkt = g.K / 64;
+  splits = std::max(1, std::min(splits, nkt));
+  a.k_per_split = (int)(round_up(nkt, splits) / splits) * 64;
+  splits = (int)((g.K + a.k_per_split - 1) / a.k_per_split);
+  if (sq && splits != 1) throw Gm2Error("bf16x3 GEMM: sums of squares need one K pass");
+  const int tiles = (g.Mp / 256) * (g.Np / 256) * splits;
+  StoreEpi ep;
+  ep.sq = sq;
+  TimedLaunch tl(kKcGemmStore, s);
+  if (g.qrow) {  // the exact 0/1 side's k-rows duplicated through the row table: a plain K-tile per (hi | lo)
+    if (g.pk || g.qk) throw Gm2Error("bf16x3 GEMM: row table with this layout not instantiated");
+    store_launch_k<Big, bf16_t, false, false, true, 2, 1, false>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
+  } else if (g.pk && g.qk) {
+    store_launch_k<Big, bf16_t, true, true, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
+  } else if (g.pk && !g.qk) {
+    store_launch_k<Big, bf16_t, true, false, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
+  } else if (!g.pk && !g.qk) {
+    store_launch_k<Big, bf16_t, false, false, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
+  } else {
+    throw Gm2Error("gemm: layout (P MN-major, Q K-major) not instantiated");
+  }
+  GM2_CHECK_LAUNCH();
+  return splits;
+}
+
+bool gemm_recon_x3_ok(const GemmArgs<bf16_t>& g) { return pp_enabled() && g.K % 64 == 0 && recon_big<bf16_t>(g); }
+
+void launch_gemm_recon_loss_x3(const GemmArgs<bf16_t>& g, const float* bias, const uint32_t* X, int64_t ldx,
+                               int with_grad, const float* scal, float* dL, int64_t ldd, int gcols, int drows,
+                               float* loss_part, float* colpart, int64_t ldcol, hipStream_t s) {
+  TimedLaunch tl(kKcReconLoss, s);
+  check_gemm(g, 256);
+  if (gcols % 128 || gcols > ldd || ldx * 32 < gcols || (ldx & 3) || (ldd & 3) || (((uintptr_t)dL) & 15))
+    throw Gm2Error("bf16x3 recon: gcols %d, ldd %lld, target pitch %lld", gcols, (long long)ldd, (long long)ldx);
+  constexpr int lds = recon_x3_lds_bytes();
+  static_assert(lds <= 160 * 1024, "LDS budget");
+  const int tiles = (g.Mp / 256) * (g.Np / 256);
+  int grid = tiles, ntiles = 0;
+  if (grid_cap_bits() & 4) {
+    const int cus = device_cus(), rounds = (tiles + cus - 1) / cus;
+    grid = (tiles + rounds - 1) / rounds;
+    ntiles = grid < tiles ? tiles : 0;
+  }
+  auto go = [&](auto kern) {
+    ensure_lds_attr((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Big::NT), lds, s, g, bias, X, ldx, ntiles, scal, dL, ldd, gcols, drows,
+                       loss_part, colpart, ldcol);
+  };
+  if (with_grad) go(k_gemm_recon_loss_x3<true>);
+  else go(k_gemm_recon_loss_x3<false>);
   GM2_CHECK_LAUNCH();
 }
 

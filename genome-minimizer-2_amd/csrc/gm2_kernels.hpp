@@ -96,6 +96,7 @@ struct Options {
   int band_cap = 65536;  // GM2_OPT_SAMPLE_BAND_CAP entries per band-list shard per decode (<= kBandShardCap;
                          //   smaller values exercise the overflow recompute)
   int single_bound_milli = 250;  // GM2_OPT_SAMPLE_SINGLE_BOUND the single tier's gate x 1000 (kSingleBound)
+  int train_split = 1;   // GM2_OPT_TRAIN_SPLIT   GM2_BF16X3: the G-wide GEMMs as split-bf16 products (0: exact fp32)
 };
 // validated edit of one option (throws on an unknown key or a bad value)
 void option_set(Options& o, int key, int value);
@@ -191,6 +192,23 @@ void launch_gemm_recon_loss(const GemmArgs<T>& g, const float* bias, const uint3
 constexpr int kMaxIdxRows = 8192;
 template <typename T>
 bool gemm_idx_ok(const GemmArgs<T>& g);
+// ---- GM2_BF16X3 (gm2.h): GEMMs over operands in the split layout of launch_split_kmajor /
+// launch_split_rows / launch_split_trans (g.K = twice the real K), always on 256x256 ping-pong tiles.
+// launch_gemm_store_x3: C = sum over each 32 k of hi.hi + hi.lo + lo.hi (fp32 accumulation), plain
+// fp32 store (one pass into C, or `splits` split-K slabs at stride slab; sq: StoreEpi::sq, one pass
+// only). With g.qrow (both MN-major): P in the split layout, Q's k-rows through the row table -- the
+// exact 0/1 input rows, each named twice, so the plain K-tile sums hi.x + lo.x. Returns the slabs.
+// gemm_x3_ok: the bf16 plan of g is a 256x256 one (and a row table fits the LDS).
+bool gemm_x3_ok(const GemmArgs<bf16_t>& g);
+int launch_gemm_store_x3(const GemmArgs<bf16_t>& g, int splits, float* C, int64_t ldc, int64_t slab, double* sq,
+                         hipStream_t s);
+// the output layer + loss epilogue in its exact form over split W9 / A5 (fp32 dL [..][ldd], stored for
+// genes < gcols (a multiple of 128, <= ldd) and strains < drows only; colpart / loss_part as
+// launch_gemm_recon_loss with 256-strain tiles); gemm_recon_x3_ok: the shape takes the 256x256 kernel
+bool gemm_recon_x3_ok(const GemmArgs<bf16_t>& g);
+void launch_gemm_recon_loss_x3(const GemmArgs<bf16_t>& g, const float* bias, const uint32_t* xbits, int64_t ldxb,
+                               int with_grad, const float* scal, float* dL, int64_t ldd, int gcols, int drows,
+                               float* loss_part, float* colpart, int64_t ldcol, hipStream_t s);
 // The bf16x3 sampling decode's error bound (api.hip decode_split3): per logit at most
 // kSplitUnit * ||a_r||_2 * ||w_g||_2 * 1.01 (Cauchy-Schwarz over the split's per-product error). The
 // gate is per 256 x 256 tile: a tile runs split when kSplitUnit * max_r ||a_r|| * max_g ||w_g|| * 1.01
@@ -338,6 +356,24 @@ void launch_bn_bwd_partial(const float* dslabs, int S, int64_t slab, const float
 // atomic max: zero it first). rows_pad % 256 == 0.
 void launch_split3(const float* X, int64_t ldx, int rows, int rows_pad, int K, bf16_t* out, int64_t ldo, float* rn,
                    unsigned* blk, hipStream_t s, bf16_t* out1 = nullptr);
+// GM2_BF16X3 operand splits (hi = bf16_rne(x), lo = bf16_rne(x - hi); everything outside the valid
+// rows x k box zero in both):
+//  * kmajor: X [rows][ldx] (k contiguous, k < K valid, K % 8 == 0, rows 16-B aligned) -> out [rows_pad][ldo]:
+//    (hi | lo) per 32 k over Kpad k (Kpad % 32 == 0, ldo >= 2 Kpad). dup: lo = hi (an operand exact
+//    in bf16 read by a plain K-tile: the sum then pairs it with the other side's hi and lo).
+//    out1 (optional): the hi parts alone, [rows_pad][ld1] over Kpad k.
+//  * rows: X [krows][ldx] (k = the row, n contiguous, n < N valid) -> out [2 kpad][ldo]: k-row k's hi
+//    part at row (k / 32) * 64 + k % 32, its lo part 32 rows further, columns up to Npad (N % 4 == 0
+//    source rows 16-B aligned, Npad % 8 == 0, kpad % 32 == 0)
+//  * trans: X [rows][ldx] (k contiguous) -> the `rows` layout with n = the source row (gm2_split_operand)
+void launch_split_kmajor(const float* X, int64_t ldx, int rows, int K, int rows_pad, int Kpad, bf16_t* out, int64_t ldo,
+                         int dup, bf16_t* out1, int64_t ld1, hipStream_t s);
+void launch_split_rows(const float* X, int64_t ldx, int krows, int N, int kpad, int Npad, bf16_t* out, int64_t ldo,
+                       hipStream_t s);
+void launch_split_trans(const float* X, int64_t ldx, int rows, int K, int rows_pad, bf16_t* out, int64_t ldo,
+                        hipStream_t s);
+// the row table of the exact side's duplicated k-rows: t[k'] = (k' / 64) * 32 + k' % 32, k' < n
+void launch_dup_rows(int32_t* t, int n, hipStream_t s);
 // dst[c][r] = src[r][c] for an R x Cn block (multiples of 64)
 template <typename T>
 void launch_transpose(const T* src, int64_t lds_, int R, int Cn, T* dst, int64_t ldd, hipStream_t s);

@@ -1107,6 +1107,95 @@ __global__ __launch_bounds__(256) void k_split3(const float* __restrict__ X, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// GM2_BF16X3 operand splits (gm2_kernels.hpp launch_split_*): hi = bf16_rne(x), lo = bf16_rne(x - hi),
+// zero outside the valid box. Streaming passes: 8 source floats per thread, 16-byte stores.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void split8(const float (&x)[8], uint4& hv, uint4& lv) {
+  uint32_t hw[4], lw[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float h0 = bf2f(f2bf(x[2 * e])), h1 = bf2f(f2bf(x[2 * e + 1]));
+    hw[e] = f2bf2(x[2 * e], x[2 * e + 1]);
+    lw[e] = f2bf2(x[2 * e] - h0, x[2 * e + 1] - h1);
+  }
+  hv = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+  lv = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+}
+
+// 8 floats of a source row at column c0, zero at and past column `valid` (or when !row_ok)
+__device__ __forceinline__ void load8(const float* __restrict__ row, int c0, int valid, bool row_ok, float (&x)[8]) {
+  if (row_ok && c0 < valid) {
+    const float4 a = *(const float4*)(row + c0), b = *(const float4*)(row + c0 + 4);
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (c0 + e >= valid) x[e] = 0.f;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = 0.f;
+  }
+}
+
+// grid (rows_pad, ceil(Kpad / 2048))
+__global__ __launch_bounds__(256) void k_split_kmajor(const float* __restrict__ X, int64_t ldx, int rows, int K, int Kpad,
+                                                    bf16_t* __restrict__ out, int64_t ldo, int dup,
+                                                    bf16_t* __restrict__ out1, int64_t ld1) {
+  const int r = blockIdx.x, k0 = (blockIdx.y * 256 + threadIdx.x) * 8;
+  if (k0 >= Kpad) return;
+  float x[8];
+  load8(X + (int64_t)r * ldx, k0, K, r < rows, x);
+  uint4 hv, lv;
+  split8(x, hv, lv);
+  bf16_t* o = out + (int64_t)r * ldo + 2 * (k0 & ~31) + (k0 & 31);
+  *(uint4*)o = hv;
+  *(uint4*)(o + 32) = dup ? hv : lv;
+  if (out1) *(uint4*)(out1 + (int64_t)r * ld1 + k0) = hv;
+}
+
+// grid (kpad, ceil(Npad / 2048))
+__global__ __launch_bounds__(256) void k_split_rows(const float* __restrict__ X, int64_t ldx, int krows, int N, int Npad,
+                                                  bf16_t* __restrict__ out, int64_t ldo) {
+  const int k = blockIdx.x, n0 = (blockIdx.y * 256 + threadIdx.x) * 8;
+  if (n0 >= Npad) return;
+  float x[8];
+  load8(X + (int64_t)k * ldx, n0, N, k < krows, x);
+  uint4 hv, lv;
+  split8(x, hv, lv);
+  bf16_t* o = out + (int64_t)((k >> 5) * 64 + (k & 31)) * ldo + n0;
+  *(uint4*)o = hv;
+  *(uint4*)(o + 32 * ldo) = lv;
+}
+
+// grid (rows_pad / 64, K / 32): a 64-row x 32-k block of X through LDS, written k-row by k-row
+__global__ __launch_bounds__(256) void k_split_trans(const float* __restrict__ X, int64_t ldx, int rows,
+                                                   bf16_t* __restrict__ out, int64_t ldo) {
+  __shared__ float tile[32][65];
+  const int r0 = blockIdx.x * 64, kt = blockIdx.y;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = j * 256 + threadIdx.x, row = i >> 3, kc = (i & 7) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r0 + row < rows) v = *(const float4*)(X + (int64_t)(r0 + row) * ldx + kt * 32 + kc);
+    tile[kc][row] = v.x; tile[kc + 1][row] = v.y; tile[kc + 2][row] = v.z; tile[kc + 3][row] = v.w;
+  }
+  __syncthreads();
+  const int k = threadIdx.x >> 3, rc = (threadIdx.x & 7) * 8;
+  float x[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = tile[k][rc + e];
+  uint4 hv, lv;
+  split8(x, hv, lv);
+  bf16_t* o = out + (int64_t)(kt * 64 + k) * ldo + r0 + rc;
+  *(uint4*)o = hv;
+  *(uint4*)(o + 32 * ldo) = lv;
+}
+
+__global__ __launch_bounds__(256) void k_dup_rows(int32_t* __restrict__ t, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) t[i] = (i >> 6) * 32 + (i & 31);
+}
+
+// ---------------------------------------------------------------------------------------------
 // bf16 gradient exchange (gm2/ddp.py bf16_exchange_sum, gm2.h gm2_exchange_*): pack rounds the fp32
 // gradient to bf16 (RNE, zero pad up to n_pad), ranksum forms out[i] = bf16(((p_0[i] + p_1[i]) + ...)
 // + p_{world-1}[i]) in fp32 in rank order from the world's received bf16 chunks, unpack widens the
@@ -1570,6 +1659,44 @@ void launch_split3(const float* X, int64_t ldx, int rows, int rows_pad, int K, b
       (((uintptr_t)out) & 15) || (((uintptr_t)out1) & 15))
     throw Gm2Error("split3: K %d, ld %lld / %lld, rows %d / %d", K, (long long)ldx, (long long)ldo, rows, rows_pad);
   hipLaunchKernelGGL(k_split3, dim3(rows_pad / 16), dim3(256), 0, s, X, ldx, rows, K, out, ldo, rn, blk, out1);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_split_kmajor(const float* X, int64_t ldx, int rows, int K, int rows_pad, int Kpad, bf16_t* out, int64_t ldo,
+                         int dup, bf16_t* out1, int64_t ld1, hipStream_t s) {
+  if (rows < 0 || rows > rows_pad || rows_pad <= 0 || K < 0 || K > Kpad || Kpad % 32 || ldx % 4 || ldx < round_up(K, 8) ||
+      ldo % 8 || ldo < 2 * (int64_t)Kpad || (out1 && (ld1 % 8 || ld1 < Kpad)) ||
+      ((((uintptr_t)X) | ((uintptr_t)out) | ((uintptr_t)out1)) & 15))
+    throw Gm2Error("split (k-major): rows %d / %d, K %d / %d, ld %lld / %lld", rows, rows_pad, K, Kpad, (long long)ldx,
+                   (long long)ldo);
+  hipLaunchKernelGGL(k_split_kmajor, dim3(rows_pad, (Kpad + 2047) / 2048), dim3(256), 0, s, X, ldx, rows, K, Kpad, out, ldo,
+                     dup, out1, ld1);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_split_rows(const float* X, int64_t ldx, int krows, int N, int kpad, int Npad, bf16_t* out, int64_t ldo,
+                       hipStream_t s) {
+  if (krows < 0 || krows > kpad || kpad <= 0 || kpad % 32 || N < 0 || N > Npad || Npad % 8 || ldx % 4 ||
+      ldx < round_up(N, 8) || ldo % 8 || ldo < Npad || ((((uintptr_t)X) | ((uintptr_t)out)) & 15))
+    throw Gm2Error("split (rows): k-rows %d / %d, N %d / %d, ld %lld / %lld", krows, kpad, N, Npad, (long long)ldx,
+                   (long long)ldo);
+  hipLaunchKernelGGL(k_split_rows, dim3(kpad, (Npad + 2047) / 2048), dim3(256), 0, s, X, ldx, krows, N, Npad, out, ldo);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_split_trans(const float* X, int64_t ldx, int rows, int K, int rows_pad, bf16_t* out, int64_t ldo,
+                        hipStream_t s) {
+  if (rows < 0 || rows > rows_pad || rows_pad <= 0 || rows_pad % 64 || K <= 0 || K % 32 || K / 32 > 65535 || ldx % 4 ||
+      ldx < K || ldo % 8 || ldo < rows_pad || ((((uintptr_t)X) | ((uintptr_t)out)) & 15))
+    throw Gm2Error("split (transposing): rows %d / %d, K %d, ld %lld / %lld", rows, rows_pad, K, (long long)ldx,
+                   (long long)ldo);
+  hipLaunchKernelGGL(k_split_trans, dim3(rows_pad / 64, K / 32), dim3(256), 0, s, X, ldx, rows, out, ldo);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_dup_rows(int32_t* t, int n, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_dup_rows, dim3((n + 255) / 256), dim3(256), 0, s, t, n);
   GM2_CHECK_LAUNCH();
 }
 

@@ -84,6 +84,10 @@ void option_set(Options& o, int key, int value) {
       if (value < 1 || value > 1000000) throw Gm2Error("single-tier bound %d (x 1e-3): 1..1000000", value);
       o.single_bound_milli = value;
       break;
+    case GM2_OPT_TRAIN_SPLIT:
+      if (value != 0 && value != 1) throw Gm2Error("train split %d: 0 or 1", value);
+      o.train_split = value;
+      break;
     default: throw Gm2Error("unknown option %d", key);
   }
 }
@@ -105,6 +109,7 @@ int option_get(const Options& o, int key) {
     case GM2_OPT_SAMPLE_SINGLE: return o.sample_single;
     case GM2_OPT_SAMPLE_BAND_CAP: return o.band_cap;
     case GM2_OPT_SAMPLE_SINGLE_BOUND: return o.single_bound_milli;
+    case GM2_OPT_TRAIN_SPLIT: return o.train_split;
     default: throw Gm2Error("unknown option %d", key);
   }
 }

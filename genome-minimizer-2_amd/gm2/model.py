@@ -67,8 +67,9 @@ def _default_device():
 
 class VAE:
     """Drop-in for the reference VAE (model.py:13). `precision` selects the GEMM arithmetic of
-    training/eval/encode (native.GM2_F32 exact fp32, native.GM2_BF16); sampling always decodes in
-    exact fp32 so its thresholded masks match the fp32 reference."""
+    training/eval/encode (native.GM2_F32 exact fp32, native.GM2_BF16, native.GM2_BF16X3 = fp32 with
+    the five gene-wide GEMMs of training / evaluation as split-bf16 products); sampling always decodes
+    in exact fp32 so its thresholded masks match the fp32 reference."""
 
     def __init__(self, input_dim, hidden_dim, latent_dim, device=None, precision=native.GM2_BF16,
                  init=True):
@@ -309,8 +310,9 @@ class VAE:
         return mu, lv
 
     def __repr__(self):
+        prec = {native.GM2_F32: "fp32", native.GM2_BF16X3: "bf16x3"}.get(self.precision, "bf16")
         return (f"VAE(input_dim={self.input_dim}, hidden_dim={self.hidden_dim}, latent_dim={self.latent_dim}, "
-                f"device={self.device}, precision={'fp32' if self.precision == native.GM2_F32 else 'bf16'})")
+                f"device={self.device}, precision={prec})")
 
 
 class _Forward(torch.autograd.Function):

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("GM2_LIB_PATH") or os.path.join(os.path.dirname(os.pat
 
 GM2_F32 = 0
 GM2_BF16 = 1
+GM2_BF16X3 = 2  # GM2_F32 except the five G-wide GEMMs of training / evaluation: split-bf16 products (gm2.h)
+PRECISION_NAMES = {GM2_F32: "f32", GM2_BF16: "bf16", GM2_BF16X3: "bf16x3"}
 NUM_PARAMS = 30
 NUM_SCALARS = 16
 LOSS_SLOTS = 8
@@ -35,7 +37,7 @@ EXPORTS = ["gm2_last_error", "gm2_abi_version", "gm2_param_count", "gm2_param_of
            "gm2_workspace_set_collective", "gm2_workspace_join",
            "gm2_resident_layout", "gm2_resident_build",
            "gm2_timing_begin", "gm2_timing_end", "gm2_timing_class", "gm2_workspace_stat",
-           "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack"]
+           "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand"]
 ABI_VERSION = 6
 KC_RECON_LOSS, KC_GEMM_STORE, KC_MASK, KC_ADAM = 1, 2, 4, 8
 OPT_GEMM_PP, OPT_SIDE_STREAM, OPT_RECON_TILE, OPT_SMALL_SPLIT, OPT_BN_EPILOGUE, OPT_SMALL_WAVES = 1, 2, 3, 4, 5, 6
@@ -44,6 +46,7 @@ OPT_GRAD_BUCKETS = 15
 OPT_SAMPLE_SPLIT = 18
 OPT_SAMPLE_SINGLE = 20
 OPT_SAMPLE_BAND_CAP, OPT_SAMPLE_SINGLE_BOUND = 21, 22
+OPT_TRAIN_SPLIT = 24
 STAT_SPLIT_DECODES, STAT_EXACT_DECODES, STAT_SPLIT_TILES, STAT_EXACT_TILES = 1, 2, 3, 4
 STAT_BAND_ELEMENTS, STAT_BAND_FLIPS, STAT_BAND_OVERFLOW, STAT_SINGLE_TILES = 5, 6, 7, 8
 STAT_OVERFLOW_TILES = 9
@@ -53,6 +56,9 @@ DECODE_STATS = {"split_decodes": STAT_SPLIT_DECODES, "exact_decodes": STAT_EXACT
                 "band_elements": STAT_BAND_ELEMENTS, "band_flips": STAT_BAND_FLIPS,
                 "band_overflow": STAT_BAND_OVERFLOW, "single_tiles": STAT_SINGLE_TILES,
                 "overflow_tiles": STAT_OVERFLOW_TILES}
+# a GM2_BF16X3 workspace's counters (gm2.h GM2_TSTAT_*): G-wide GEMMs run as split-bf16 products / exact fp32
+TSTAT_SPLIT_GEMMS, TSTAT_EXACT_GEMMS = 32, 33
+TRAIN_STATS = {"split_gemms": TSTAT_SPLIT_GEMMS, "exact_gemms": TSTAT_EXACT_GEMMS}
 # gm2_allreduce_fn (gm2.h): int (double* buf, int64_t count, void* stream, void* user)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -124,6 +130,7 @@ def lib():
         "gm2_exchange_pack": (C.c_int, [vp, i64, vp, i64, vp]),
         "gm2_exchange_ranksum": (C.c_int, [vp, i32, i64, vp, vp]),
         "gm2_exchange_unpack": (C.c_int, [vp, i64, vp, vp]),
+        "gm2_split_operand": (C.c_int, [vp, i64, i64, i64, i32, vp, i64, vp]),
         "gm2_timing_begin": (C.c_int, [i32]),
         "gm2_timing_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
         "gm2_timing_class": (C.c_int, [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -204,7 +211,7 @@ class Workspace:
         check(lib().gm2_workspace_join(self.ptr, stream()), "gm2_workspace_join")
 
     def stat(self, key: int) -> int:
-        """A counter of this workspace's host-side state (gm2.h GM2_STAT_*)."""
+        """A counter of this workspace's host-side state (gm2.h GM2_STAT_* / GM2_TSTAT_*)."""
         v = C.c_int64()
         check(lib().gm2_workspace_stat(self.ptr, int(key), C.byref(v)), "gm2_workspace_stat")
         return int(v.value)
@@ -380,6 +387,18 @@ def recon_counts(ws: Workspace, batch: Batch, params, bn, threshold, counts):
 def gemm(prec, P, ldp, Q, ldq, Cout, ldc, M, N, K, splits=1, slab=None, p_kmajor=True, q_kmajor=True):
     check(lib().gm2_gemm(prec, int(p_kmajor), int(q_kmajor), ptr(P), ldp, ptr(Q), ldq, ptr(Cout), ldc, M, N, K,
                          splits, ptr(slab), stream()), "gm2_gemm")
+
+
+def split_operand(x, kmajor: bool = True):
+    """The bf16x3 split of an fp32 [rows][K] device matrix (K % 32 == 0) as gm2_gemm(GM2_BF16X3) reads it
+    (gm2_split_operand): a bf16 tensor [roundup(rows, 256)][2K] (hi | lo per 32 k) when kmajor, else
+    [2K][roundup(rows, 256)] (hi | lo per 32 k-rows)."""
+    rows, K = x.shape
+    rp = (rows + 255) // 256 * 256
+    out = torch.empty((rp, 2 * K) if kmajor else (2 * K, rp), dtype=torch.bfloat16, device=x.device)
+    check(lib().gm2_split_operand(ptr(x), x.stride(0), rows, K, int(kmajor), ptr(out), out.stride(0), stream()),
+          "gm2_split_operand")
+    return out
 
 
 GRAD_BUCKETS = 6

@@ -36,8 +36,17 @@ extern "C" {
 #define GM2_NUM_SCALARS 16
 
 /* arithmetic of the GEMMs: GM2_F32 = exact fp32 MFMA (parity / sampling), GM2_BF16 = bf16 MFMA
- * with fp32 accumulation, fp32 master weights and fp32 BatchNorm / loss / optimizer math */
-enum { GM2_F32 = 0, GM2_BF16 = 1 };
+ * with fp32 accumulation, fp32 master weights and fp32 BatchNorm / loss / optimizer math.
+ * GM2_BF16X3 (ABI 6, additive) = GM2_F32 in everything (workspace element type, hidden layers,
+ * BatchNorm, heads, the exact BCE epilogue, fp32 dL, clip norm, Adam) except the five GEMMs with a
+ * G-wide side -- input layer, output layer + loss, the output layer's input gradient and the two big
+ * weight gradients -- which gm2_train_fwd_bwd and gm2_eval_forward run as split-bf16 products on
+ * the bf16 MFMA: each fp32 operand x becomes hi = bf16_rne(x), lo = bf16_rne(x - hi) and the GEMM
+ * sums hi.hi + hi.lo + lo.hi in fp32 (the 0/1 input rows are exact in bf16: two products). A GEMM
+ * whose shape gets no 256 x 256 plan (small batches, H % 256 != 0) runs the exact-fp32 kernel
+ * (GM2_TSTAT_*). Every other entry point that takes a precision treats GM2_BF16X3 as GM2_F32. The
+ * workspace is the GM2_F32 layout plus the split operand buffers. */
+enum { GM2_F32 = 0, GM2_BF16 = 1, GM2_BF16X3 = 2 };
 
 /* model + call geometry. G = genes (input_dim), H = hidden_dim (multiple of 128),
  * L = latent_dim (divides 256), batch_max = the largest row count any call will pass. */
@@ -257,13 +266,26 @@ int gm2_backward_outputs(const gm2_dims* d, int precision, const gm2_batch* batc
 int gm2_reparameterize(int64_t n, const float* mu, const float* logvar, const float* eps, float* z,
                        const float* dz, float* dmu, float* dlogvar, void* stream);
 
+/* (ABI 6, additive) The bf16x3 split of an fp32 operand X [rows][ldx] (K contiguous, K % 32 == 0) as
+ * GM2_BF16X3's GEMMs read it: hi = bf16_rne(x), lo = bf16_rne(x - hi), pads zero in both.
+ *   kmajor = 1: out [roundup(rows, 256)][ldo], ldo >= 2K: element (r, k) has its hi part at
+ *               out[r * ldo + (k / 32) * 64 + k % 32] and its lo part 32 elements further.
+ *   kmajor = 0: out [2K][ldo], ldo >= roundup(rows, 256), ldo % 8 == 0: element (r, k) has its hi part
+ *               at out[((k / 32) * 64 + k % 32) * ldo + r] and its lo part 32 k-rows further.
+ * Every element of out up to column 2K (kmajor) / roundup(rows, 256) (MN-major) is written. */
+int gm2_split_operand(const float* X, int64_t ldx, int64_t rows, int64_t K, int kmajor, uint16_t* out, int64_t ldo,
+                      void* stream);
+
 /* Raw GEMM primitive, exposed for kernel-level tests: C[M][ldc] (fp32) = sum_k P(m,k) Q(n,k).
  * p_kmajor / q_kmajor = 1: the operand is stored [rows][ld] with K contiguous (P(m,k) = P[m*ld+k]);
  * 0: stored [K][ld] with M (N) contiguous (P(m,k) = P[k*ld+m]). Elements of `precision` type;
  * the M (N) extent is padded to a multiple of 128 in the allocation, K % 64 == 0, pads zero.
  * (P MN-major with Q K-major is not instantiated.) splits 0/1: one pass straight into C; > 1: that
  * many split-K slices; < 0: the hot path's own tile / split plan (at most 32 slices). Split runs
- * need slab_ws (fp32, splits * M * ldc elements) and sum the slices into C. */
+ * need slab_ws (fp32, splits * M * ldc elements) and sum the slices into C.
+ * precision GM2_BF16X3: P and Q are gm2_split_operand outputs (same p_kmajor / q_kmajor), K is the
+ * real K (K % 32 == 0), the M / N extents are padded to 256 in the allocation; always the 256 x 256
+ * split kernel (hi.hi + hi.lo + lo.hi per 32 k, fp32 accumulation), splits as above. */
 int gm2_gemm(int precision, int p_kmajor, int q_kmajor, const void* P, int64_t ldp, const void* Q,
              int64_t ldq, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int splits,
              float* slab_ws, void* stream);
@@ -345,7 +367,11 @@ int gm2_gemm(int precision, int p_kmajor, int q_kmajor, const void* P, int64_t l
  *                       masks do not depend on this value; smaller values exercise that path.
  *   GM2_OPT_SAMPLE_SINGLE_BOUND (ABI 6) the single tier's gate x 1000 (default 250 = 0.25, 1..1e6):
  *                       larger values send more tiles to the single tier (a wider band; a tile
- *                       whose band overflows its slots re-runs as bf16x3). Cost only, never the masks. */
+ *                       whose band overflows its slots re-runs as bf16x3). Cost only, never the masks.
+ *   GM2_OPT_TRAIN_SPLIT (ABI 6, additive; workspace option) 1 (default) = a GM2_BF16X3 workspace runs its five
+ *                       G-wide GEMMs as split-bf16 products where the shape gets a 256 x 256 plan;
+ *                       0 = the exact-fp32 GEMMs everywhere: GM2_F32 bit for bit. Other values
+ *                       are refused. No effect on GM2_F32 / GM2_BF16 workspaces. */
 enum {
   GM2_OPT_GEMM_PP = 1,
   GM2_OPT_SIDE_STREAM = 2,
@@ -361,7 +387,8 @@ enum {
   GM2_OPT_SAMPLE_SPLIT = 18,
   GM2_OPT_SAMPLE_SINGLE = 20,
   GM2_OPT_SAMPLE_BAND_CAP = 21,
-  GM2_OPT_SAMPLE_SINGLE_BOUND = 22
+  GM2_OPT_SAMPLE_SINGLE_BOUND = 22,
+  GM2_OPT_TRAIN_SPLIT = 24
 };
 int gm2_set_option(int key, int value);
 int gm2_get_option(int key, int* value);
@@ -399,6 +426,11 @@ enum {
   GM2_STAT_OVERFLOW_TILES = 9
 };
 int gm2_workspace_stat(void* ws, int key, int64_t* value);
+/* (ABI 6, additive) counters of a GM2_BF16X3 workspace's gm2_train_fwd_bwd / gm2_eval_forward calls,
+ * read through gm2_workspace_stat, cumulative since gm2_workspace_init (host counters: no device
+ * wait): how many of the G-wide GEMMs (five per training call, two per evaluation) ran as split-bf16
+ * products, and how many as the exact-fp32 kernel (no 256 x 256 plan, or GM2_OPT_TRAIN_SPLIT off) */
+enum { GM2_TSTAT_SPLIT_GEMMS = 32, GM2_TSTAT_EXACT_GEMMS = 33 };
 
 /* The all-reduce SyncBN needs (GM2_OPT_SYNC_BN), supplied by the caller: SUM `count` doubles at the
  * DEVICE pointer `buf` (inside the workspace) across every rank, in place, ordered on `stream` (the

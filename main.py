@@ -25,7 +25,7 @@ rank 0 prints and saves the checkpoint (--sync-bn: BatchNorm over the global bat
 contiguous slice on its GPU, rank 0 gathers the packed masks and writes the files. Other modes run
 on rank 0 only.
 
-Additions (no reference equivalent): --precision bf16|f32 for the training GEMMs (sampling always
+Additions (no reference equivalent): --precision bf16|bf16x3|f32 for the training GEMMs (sampling always
 decodes in exact fp32), --mask-dtype float64|uint8|bits for the saved masks (the reference writes
 float64 via `.astype(float)`, main.py:369-371 / extras.py:200-201; uint8 keeps 1e6-genome runs in
 memory; bits = numpy packbits(bitorder='little') rows, 1/64 of float64, accepted by convert-samples),
@@ -58,7 +58,7 @@ def parse_arguments(argv=None):
     p.add_argument("--sampling-mode", choices=["default", "focused"], default="default")
     p.add_argument("--noise-level", type=float, default=0.1)
     p.add_argument("--project-root", type=str, default=os.environ.get("GM2_PROJECT_ROOT", os.getcwd()))
-    p.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
+    p.add_argument("--precision", choices=["bf16", "bf16x3", "f32"], default="bf16")
     p.add_argument("--grad-exchange", choices=["f32", "bf16"], default=None,
                    help="torchrun / DDP only: dtype of the big weight-gradient all-reduce (default f32)")
     p.add_argument("--sync-bn", action="store_true",
@@ -96,13 +96,15 @@ def check_data_availability(root):
 PRECISION_NOTE = {
     "bf16": "bf16 GEMM operands, fp32 accumulation; fp32 master weights, BatchNorm, losses and Adam "
             "(--precision f32: the reference's fp32 arithmetic)",
+    "bf16x3": "fp32 throughout, except the five gene-wide GEMMs of a step: fp32 operands split into bf16 hi + lo, "
+              "hi.hi + hi.lo + lo.hi accumulated in fp32 (about 500x tighter than bf16; f32 is the reference's arithmetic)",
     "f32": "fp32 throughout (the reference's arithmetic)",
 }
 
 
 def _precision(args):
     from gm2 import native
-    return native.GM2_F32 if args.precision == "f32" else native.GM2_BF16
+    return {"f32": native.GM2_F32, "bf16x3": native.GM2_BF16X3}.get(args.precision, native.GM2_BF16)
 
 
 def run_single_experiment(args):

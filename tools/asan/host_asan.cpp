@@ -57,9 +57,13 @@ static void dims_and_layouts() {
           CHECK(gm2_grad_bucket_bounds(&d, lh.data()) == 0, "bucket bounds");
           for (int b = 0; b < GM2_GRAD_BUCKETS; ++b)
             CHECK(0 <= lh[2 * b] && lh[2 * b] <= lh[2 * b + 1] && lh[2 * b + 1] <= n, "bucket %d in range", b);
-          for (int prec : {GM2_F32, GM2_BF16}) {
+          size_t f32_bytes = 0;
+          for (int prec : {GM2_F32, GM2_BF16, GM2_BF16X3}) {
             size_t bytes = 0;
             CHECK(gm2_workspace_size(&d, prec, &bytes) == 0, "workspace_size %s", gm2_last_error());
+            // (GM2_BF16X3: the GM2_F32 layout plus the split operand buffers)
+            if (prec == GM2_F32) f32_bytes = bytes;
+            if (prec == GM2_BF16X3) CHECK(bytes > f32_bytes, "bf16x3 workspace %zu vs f32 %zu", bytes, f32_bytes);
             int64_t nreg = 0, total = 0;
             const int rc = gm2_debug_check_layout(&d, prec, &nreg, &total);
             CHECK(rc == 0, "layout G=%lld H=%lld L=%lld B=%lld prec=%d: %s", (long long)G, (long long)H,
@@ -77,6 +81,9 @@ static void dims_and_layouts() {
   expect_error(gm2_workspace_size(nullptr, GM2_BF16, &bytes), "null dims", "null dims");
   gm2_dims d{100, 128, 8, 16};
   expect_error(gm2_workspace_size(&d, 7, &bytes), "precision", "bad precision");
+  expect_error(gm2_workspace_size(&d, 3, &bytes), "bad precision", "precision 3");
+  int64_t nreg = 0, total = 0;
+  expect_error(gm2_debug_check_layout(&d, 3, &nreg, &total), "bad precision", "layout of precision 3");
   // resident layouts
   for (int64_t S : {1, 2, 63, 64, 10000})
     for (int64_t G : {1, 255, 256, 20000, 55039})
@@ -95,7 +102,8 @@ static void dims_and_layouts() {
 static const int kKeys[] = {GM2_OPT_GEMM_PP,      GM2_OPT_SIDE_STREAM,  GM2_OPT_RECON_TILE,        GM2_OPT_SMALL_SPLIT,
                             GM2_OPT_BN_EPILOGUE,  GM2_OPT_SMALL_WAVES,  GM2_OPT_INPUT_CHUNKS,      GM2_OPT_GRID_CAP,
                             GM2_OPT_SYNC_BN,      GM2_OPT_DEFER_OUTPUT_ADAM, GM2_OPT_GRAD_BUCKETS, GM2_OPT_SAMPLE_SPLIT,
-                            GM2_OPT_SAMPLE_SINGLE, GM2_OPT_SAMPLE_BAND_CAP, GM2_OPT_SAMPLE_SINGLE_BOUND};
+                            GM2_OPT_SAMPLE_SINGLE, GM2_OPT_SAMPLE_BAND_CAP, GM2_OPT_SAMPLE_SINGLE_BOUND,
+                            GM2_OPT_TRAIN_SPLIT};
 
 static void options() {
   std::vector<int> saved;
@@ -129,6 +137,18 @@ static void options() {
     expect_error(gm2_set_option(bad, 1), "unknown option", "set unknown key");
     expect_error(gm2_get_option(bad, &v), "unknown option", "get unknown key");
   }
+  // GM2_OPT_TRAIN_SPLIT: default 1, 0 and 1 accepted, anything else refused and the value kept
+  {
+    int v = -1;
+    gm2_set_option(GM2_OPT_TRAIN_SPLIT, 1);
+    CHECK(gm2_set_option(GM2_OPT_TRAIN_SPLIT, 0) == 0 && gm2_get_option(GM2_OPT_TRAIN_SPLIT, &v) == 0 && v == 0,
+          "train split off");
+    for (int bad : {-1, 2, 3, 256})
+      expect_error(gm2_set_option(GM2_OPT_TRAIN_SPLIT, bad), "train split", "train split value");
+    CHECK(gm2_get_option(GM2_OPT_TRAIN_SPLIT, &v) == 0 && v == 0, "a refused train split value changed it");
+    CHECK(gm2_set_option(GM2_OPT_TRAIN_SPLIT, 1) == 0 && gm2_get_option(GM2_OPT_TRAIN_SPLIT, &v) == 0 && v == 1,
+          "train split on");
+  }
   for (size_t i = 0; i < saved.size(); ++i) gm2_set_option(kKeys[i], saved[i]);
   // per-workspace entry points on a workspace libgm2 never initialised
   char host_buf[64];
@@ -141,6 +161,7 @@ static void options() {
   expect_error(gm2_workspace_set_collective(ws, nullptr, nullptr), "not initialised", "collective");
   int64_t stat = 0;
   expect_error(gm2_workspace_stat(ws, GM2_STAT_SPLIT_DECODES, &stat), "not initialised", "stat");
+  expect_error(gm2_workspace_stat(ws, GM2_TSTAT_SPLIT_GEMMS, &stat), "not initialised", "train stat");
   CHECK(gm2_workspace_release(ws) == 0, "release of unknown state is a no-op");
 }
 
@@ -166,6 +187,14 @@ static void error_paths() {
   CHECK(gm2_grad_norm(nullptr, GM2_BF16, &f, &f, &f, loss, host.data(), nullptr) != 0, "grad_norm null dims");
   CHECK(gm2_adam_step(nullptr, GM2_BF16, &f, &f, &f, &f, &f, host.data(), nullptr) != 0, "adam null dims");
   CHECK(gm2_sync_shadows(&d, 5, &f, host.data(), nullptr) != 0, "sync_shadows bad precision");
+  CHECK(gm2_train_fwd_bwd(&d, GM2_BF16X3, &b, &f, &f, &f, &f, loss, host.data(), nullptr) != 0, "bf16x3 empty batch");
+  CHECK(gm2_eval_forward(&d, GM2_BF16X3, &b, &f, &f, &f, loss, host.data(), nullptr) != 0, "bf16x3 eval empty batch");
+  uint16_t h16 = 0;
+  CHECK(gm2_split_operand(nullptr, 32, 4, 32, 1, &h16, 64, nullptr) != 0, "split operand null input");
+  CHECK(gm2_split_operand(&f, 32, 4, 33, 1, &h16, 64, nullptr) != 0, "split operand K not a multiple of 32");
+  CHECK(gm2_split_operand(&f, 32, 0, 32, 0, &h16, 256, nullptr) != 0, "split operand no rows");
+  CHECK(gm2_gemm(GM2_BF16X3, 1, 1, &h16, 64, &h16, 64, &f, 4, 4, 4, 33, 1, nullptr, nullptr) != 0, "bf16x3 gemm K not a multiple of 32");
+  CHECK(gm2_gemm(3, 1, 1, &h16, 64, &h16, 64, &f, 4, 4, 4, 32, 1, nullptr, nullptr) != 0, "gemm precision 3");
   int64_t ld = 0, ldb = 0, rows = 0;
   size_t nb = 0, nbb = 0;
   CHECK(gm2_resident_layout(-1, 10, GM2_BF16, &ld, &ldb, &rows, &nb, &nbb) != 0, "negative S");
