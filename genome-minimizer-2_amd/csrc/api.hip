@@ -506,37 +506,38 @@ void bucket_bounds(const Dims& d, int64_t* lh) {
   }
 }
 
-// GEMM into the fp32 slab scratch (split-K slices summed by the consumer). Returns #slabs.
-template <typename T>
-int gemm_to_slabs(const Ctx<T>& c, const T* P, int64_t ldp, int Mp, const T* Q, int64_t ldq, int Np, int M, int N,
-                  int K, int64_t ldc, int pk = 1, int qk = 1, const int32_t* prow = nullptr) {
-  GemmArgs<T> g{P, ldp, Q, ldq, M, N, K, Mp, Np, 0, pk, qk};
-  g.prow = prow;
-  if (prow) g.idx_lim = c.res_rows;
-  const int64_t slab = (int64_t)Mp * ldc;
-  // (the plan's split count, at most what the stream's slab scratch holds)
-  const int S = (int)std::min<int64_t>(plan_gemm<T>(g).splits, c.slab_cap / std::max<int64_t>(slab, 1));
-  if (S < 1) throw Gm2Error("slab capacity exceeded");
-  return launch_gemm_store<T>(g, S, c.f(c.slab_off), nullptr, 0, ldc, slab, nullptr, c.s);
+// one fp32-store launch of g: plain, or (s3, GM2_BF16X3 operands in the split layout) the bf16x3 launcher
+template <typename U>
+int gemm_store(const GemmArgs<U>& g, bool s3, int S, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
+               hipStream_t s) {
+  if constexpr (sizeof(U) == 2) {
+    if (s3) return launch_gemm_store_x3(g, S, C0, ldc, slab, nullptr, s);
+  }
+  if (s3) throw Gm2Error("bf16x3 GEMM: bf16 operands only");
+  return launch_gemm_store<U>(g, S, C0, C1, msplit, ldc, slab, nullptr, s);
 }
 
-// GEMM into C0/C1 (fp32, row split at msplit). Launches with too few tiles to fill the chip are
-// split over K into slabs and summed by k_slab_sum (deterministic order).
-template <typename T>
-void gemm_to(const Ctx<T>& c, const T* P, int64_t ldp, int Mp, const T* Q, int64_t ldq, int Np, int M, int N, int K,
-             float* C0, float* C1, int msplit, int64_t ldc, int pk = 1, int qk = 1, const int32_t* qrow = nullptr) {
-  GemmArgs<T> g{P, ldp, Q, ldq, M, N, K, Mp, Np, 0, pk, qk};
-  g.qrow = qrow;
-  if (qrow) g.idx_lim = c.res_rows;
-  int S = plan_gemm<T>(g).splits;
-  const int64_t slab = round_up((int64_t)M * N, 4);
-  if ((int64_t)S * slab > c.slab_cap) S = 1;
+// GEMM into the stream's fp32 slab scratch (split-K slices summed by the consumer): the plan's
+// split count, at most what the scratch holds. Returns #slabs.
+template <class CtxT, typename U>
+int gemm_to_slabs(const CtxT& c, const GemmArgs<U>& g, int64_t ldc, bool s3 = false) {
+  const int64_t slab = slab_elems_padded(g.Mp, ldc);
+  const int S = splits_into_slabs(plan_gemm<U>(g).splits, slab, c.slab_cap);
+  return gemm_store<U>(g, s3, S, c.f(c.slab_off), nullptr, 0, ldc, slab, c.s);
+}
+
+// GEMM into C0/C1 (fp32, row split at msplit; s3: C0 only). Launches with too few tiles to fill the
+// chip are split over K into slabs and summed by k_slab_sum (deterministic order).
+template <class CtxT, typename U>
+void gemm_to(const CtxT& c, const GemmArgs<U>& g, float* C0, float* C1, int msplit, int64_t ldc, bool s3 = false) {
+  const int64_t slab = slab_elems_dense(g.M, g.N);
+  int S = splits_into_c(plan_gemm<U>(g).splits, slab, c.slab_cap, s3);
   if (S <= 1) {
-    launch_gemm_store<T>(g, 1, C0, C1, msplit, ldc, 0, nullptr, c.s);
+    gemm_store<U>(g, s3, 1, C0, C1, msplit, ldc, 0, c.s);
     return;
   }
-  S = launch_gemm_store<T>(g, S, c.f(c.slab_off), nullptr, 0, N, slab, nullptr, c.s);
-  launch_slab_sum(c.f(c.slab_off), S, slab, M, N, C0, C1, C1 ? msplit : M, ldc, c.s);
+  S = gemm_store<U>(g, s3, S, c.f(c.slab_off), nullptr, 0, g.N, slab, c.s);
+  launch_slab_sum(c.f(c.slab_off), S, slab, g.M, g.N, C0, C1, C1 ? msplit : g.M, ldc, c.s);
 }
 
 // The two big weight-gradient GEMMs of the backward (output layer dW9, stored transposed; input
@@ -593,7 +594,9 @@ void linear_pre_bn(const Ctx<T>& c, const T* in, int64_t ldin, int Bp, const T* 
   bn.part = (float2*)part;
   bn.ldp = H;
   if (!prow && launch_gemm_bn<T>(g, Y, H, bias, bn, c.s)) return;
-  const int S = gemm_to_slabs<T>(c, in, ldin, Bp, W, ldw, H, B, H, K, H, 1, 1, prow);
+  g.prow = prow;
+  if (prow) g.idx_lim = c.res_rows;
+  const int S = gemm_to_slabs(c, g, H);
   launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)Bp * H, H, bias, B, H, Y, part, c.s);
 }
 
@@ -615,13 +618,6 @@ struct X3Plan {
   int count() const { return (int)enc0 + (int)loss + (int)da5 + (int)dw9 + (int)dwe0; }
 };
 
-// split-K slices of a split GEMM stored into C: the plan's, at most what the slab scratch holds
-inline int x3_store_splits(int64_t slab_cap, const GemmArgs<bf16_t>& g) {
-  const int S = plan_gemm<bf16_t>(g).splits;
-  const int64_t slab = round_up((int64_t)g.M * g.N, 4);
-  return (int64_t)S * slab > slab_cap ? (int)std::max<int64_t>(1, slab_cap / slab) : S;
-}
-
 template <typename T>
 X3Plan x3_plan(const Ctx<T>& c, int B) {
   X3Plan p;
@@ -642,34 +638,12 @@ X3Plan x3_plan(const Ctx<T>& c, int B) {
   p.da5 = gemm_x3_ok(p.g_da5);
   p.dw9 = gemm_x3_ok(p.g_dw9);
   p.dwe0 = gemm_x3_ok(p.g_dwe0);
-  if (p.dwe0) {  // (its row table holds one slice's k-rows in LDS: the slices the launch will really take)
-    const int nkt = p.g_dwe0.K / 64, S = std::min(x3_store_splits(c.lo.slab_cap, p.g_dwe0), nkt);
-    p.dwe0 = (int)(round_up(nkt, S) / S) * 64 <= kMaxIdxRows;
+  if (p.dwe0) {  // (the slab-capped count, as gemm_to takes it: the slices the launch will really have)
+    const GemmArgs<bf16_t>& g = p.g_dwe0;
+    const int S = splits_into_c(plan_gemm<bf16_t>(g).splits, slab_elems_dense(g.M, g.N), c.lo.slab_cap, true);
+    p.dwe0 = row_table_fits(g.K, 64, S);
   }
   return p;
-}
-
-// a split GEMM into the fp32 slab scratch (plain or, s3, three-product K-tiles). Returns #slabs.
-template <typename T>
-int x3_gemm_to_slabs(const Ctx<T>& c, const GemmArgs<bf16_t>& g, int64_t ldc, bool s3) {
-  const int64_t slab = (int64_t)g.Mp * ldc;
-  const int S = (int)std::min<int64_t>(plan_gemm<bf16_t>(g).splits, c.slab_cap / std::max<int64_t>(slab, 1));
-  if (S < 1) throw Gm2Error("slab capacity exceeded");
-  if (s3) return launch_gemm_store_x3(g, S, c.f(c.slab_off), ldc, slab, nullptr, c.s);
-  return launch_gemm_store<bf16_t>(g, S, c.f(c.slab_off), nullptr, 0, ldc, slab, nullptr, c.s);
-}
-
-// a split GEMM into C (fp32 [M][ldc]); short-grid plans go through split-K slabs like gemm_to
-template <typename T>
-void x3_gemm_to(const Ctx<T>& c, const GemmArgs<bf16_t>& g, float* C, int64_t ldc) {
-  int S = x3_store_splits(c.slab_cap, g);
-  const int64_t slab = round_up((int64_t)g.M * g.N, 4);
-  if (S <= 1) {
-    launch_gemm_store_x3(g, 1, C, ldc, 0, nullptr, c.s);
-    return;
-  }
-  S = launch_gemm_store_x3(g, S, c.f(c.slab_off), g.N, slab, nullptr, c.s);
-  launch_slab_sum(c.f(c.slab_off), S, slab, g.M, g.N, C, nullptr, g.M, ldc, c.s);
 }
 
 // Tensor tables. kind 0: the 9 Linear weights with their natural-layout shadow (tile0 counts
@@ -778,7 +752,7 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   const int64_t Gq = l.Gq;
   for (int i = 0; i < 6; ++i) {
     if (i == 3) {
-      const int S = gemm_to_slabs<T>(c, c.t(l.A[2]), H, Bp, c.t(l.sHD), H, (int)d.L2r, B, 2 * L, H, 2 * L);
+      const int S = gemm_to_slabs(c, GemmArgs<T>{c.t(l.A[2]), H, c.t(l.sHD), H, B, 2 * L, H, Bp, (int)d.L2r, 0}, 2 * L);
       launch_reparam<T>(c.f(l.slabs), S, (int64_t)Bp * 2 * L, L, prm + d.off[MUB], prm + d.off[LVB], b->eps, B, Bp,
                         c.f(l.HD), c.t(l.Z), d.Lr, nullptr, 0, 0, c.f(l.klpart), c.s);
       in = c.t(l.Z);
@@ -791,7 +765,7 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
       launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1,
                           with_grad && xp.dwe0 ? c.h(l.x3x) : nullptr, Gq, c.s);
       launch_split_kmajor(c.f(l.sE0), d.Gp, H, (int)d.G, H, (int)Gq, c.h(l.x3w0), 2 * Gq, 0, nullptr, 0, c.s);
-      const int S = x3_gemm_to_slabs<T>(c, xp.g_enc0, H, false);
+      const int S = gemm_to_slabs(c, xp.g_enc0, H);
       launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)xp.Bq * H, H, prm + d.off[kBlk[i][1]], B, H, c.f(l.Y[i]),
                             c.f(l.bnpart), c.s);
     } else {
@@ -962,14 +936,14 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     if (xp.dw9) {  // bf16x3: dL and A5 as MN-major splits (k = the batch row), both made on this stream
       launch_split_rows(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlm), Gq, s9);
       launch_split_rows(c.f(l.A[5]), H, B, H, xp.Bq, H, c.h(l.x3a5m), H, s9);
-      x3_gemm_to<T>(w, xp.g_dw9, gr + d.off[D9W], H);
+      gemm_to(w, xp.g_dw9, gr + d.off[D9W], nullptr, 0, H, true);
     } else if (direct9) {
       // (A5^T here on the side stream; on the main stream before the fork measured ~35 us/step
       // slower, profiles/r02_a5t_placement_ab.txt)
       launch_transpose<T>(c.t(l.A[5]), H, Bp, H, c.t(l.AT5), Bp, s9);
       launch_gemm_trans<T>(g9, gr + d.off[D9W], H, s9, bg.direct ? nasq : nullptr);
     } else {
-      gemm_to<T>(w, c.t(l.dL), Gp, Gp, c.t(l.A[5]), H, H, G, H, Bp, gr + d.off[D9W], nullptr, 0, H, 0, 0);
+      gemm_to(w, GemmArgs<T>{c.t(l.dL), Gp, c.t(l.A[5]), H, G, H, Bp, Gp, H, 0, 0, 0}, gr + d.off[D9W], nullptr, 0, H);
     }
     if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[0], s9));
   };
@@ -993,13 +967,13 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     bn.beta = prm + d.off[kBlk[j][3]];
     bn.H = H;
     have_part = launch_gemm_bn<T>(g, c.f(c.slab_off), H, nullptr, bn, c.s);
-    return have_part ? 1 : gemm_to_slabs<T>(c, dY, lddy, Bp, W, ldw, H, B, H, K, H, 1, 0);
+    return have_part ? 1 : gemm_to_slabs(c, g, H);
   };
   int S;
   if (xp.da5) {  // bf16x3: dL K-major and W9 MN-major (its natural [G][H] rows interleaved), to slabs
     launch_split_kmajor(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlk), 2 * (int64_t)Gq, 0, nullptr, 0, c.s);
     launch_split_rows(c.f(l.sD3), H, G, H, Gq, H, c.h(l.x3w9m), H, c.s);
-    S = x3_gemm_to_slabs<T>(c, xp.g_da5, H, true);
+    S = gemm_to_slabs(c, xp.g_da5, H, true);
   } else {
     S = dx_pre_bn(c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
   }
@@ -1042,7 +1016,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
       if (xp.dwe0) {  // bf16x3: dY0 as an MN-major split, X's rows (exact in bf16) named twice by the row table
         launch_split_rows(c.f(l.dY[0]), H, B, H, xp.Bq, H, c.h(l.x3dy0), H, c.s);
         launch_dup_rows((int32_t*)(c.ws + l.x3rows), 2 * xp.Bq, c.s);
-        x3_gemm_to<T>(c, xp.g_dwe0, gr + d.off[E0W], G);
+        gemm_to(c, xp.g_dwe0, gr + d.off[E0W], nullptr, 0, G, true);
         if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2], c.s));
         for (int q = 0; q < 4; ++q) st.bucket_ev[2 + q] = 2;
       } else if (input_chunked(bg, H)) {  // four row-quarter launches, bucket 2 + q final after launch q
@@ -1058,8 +1032,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
         }
       } else {
         if (!bg.direct || !launch_gemm_sq<T>(bg.g0, gr + d.off[E0W], G, nasq + bg.n9, c.s, false))
-          gemm_to<T>(c, c.t(l.dYT0), Bp, H, bg.g0.Q, bg.g0.ldq, Gp, H, G, Bp, gr + d.off[E0W], nullptr, 0, G, 1, 0,
-                     bg.g0.qrow);
+          gemm_to(c, bg.g0, gr + d.off[E0W], nullptr, 0, G);
         // one launch: buckets 2..5 become final together, one event marks all four
         if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2], c.s));
         for (int q = 0; q < 4; ++q) st.bucket_ev[2 + q] = 2;
@@ -1084,23 +1057,26 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
       break;
     }
     if (i == 3) {  // decoder input layer, then back through the reparameterisation and the heads
-      side_work(3 >= hold_from, [&, dY] { gemm_to<T>(w, dY, H, H, c.t(l.Z), Lr, Lr, H, L, Bp, gr + d.off[D0W], nullptr, 0, L, 0, 0); });
-      S = gemm_to_slabs<T>(c, dY, H, Bp, c.t(l.sD0), Lr, Lr, B, L, H, L, 1, 0);
+      side_work(3 >= hold_from, [&, dY] {
+        gemm_to(w, GemmArgs<T>{dY, H, c.t(l.Z), Lr, H, L, Bp, H, Lr, 0, 0, 0}, gr + d.off[D0W], nullptr, 0, L);
+      });
+      S = gemm_to_slabs(c, GemmArgs<T>{dY, H, c.t(l.sD0), Lr, B, L, H, Bp, Lr, 0, 1, 0}, L);
       float* colh = c.f(l.colbwd) + 6 * l.colbwd_cap;
       launch_reparam_bwd<T>(c.f(c.slab_off), S, (int64_t)Bp * L, L, c.f(l.HD), b->eps, scal, B, Bp, L, c.t(l.dH),
                             L2r, dmu_ext, dlv_ext, colh, c.s);
       fork_flush(3 >= hold_from);
       side_work(3 >= hold_from, [&, colh] {
         launch_colsum(colh, Bp / kReparamRows, 2 * L, 2 * L, gr + d.off[MUB], gr + d.off[LVB], L, w.s);
-        gemm_to<T>(w, c.t(l.dH), L2r, L2r, c.t(l.A[2]), H, H, 2 * L, H, Bp, gr + d.off[MUW], gr + d.off[LVW], L, H,
-                   0, 0);
+        gemm_to(w, GemmArgs<T>{c.t(l.dH), L2r, c.t(l.A[2]), H, 2 * L, H, Bp, L2r, H, 0, 0, 0}, gr + d.off[MUW],
+                gr + d.off[LVW], L, H);
       });
       S = dx_pre_bn(c.t(l.dH), L2r, c.t(l.sHD), H, (int)d.K2L, 2);
       chain_mark();
       continue;
     }
     side_work(hold, [&, dY, i] {
-      gemm_to<T>(w, dY, H, H, c.t(l.A[i - 1]), H, H, H, H, Bp, gr + d.off[kBlk[i][0]], nullptr, 0, H, 0, 0);
+      gemm_to(w, GemmArgs<T>{dY, H, c.t(l.A[i - 1]), H, H, H, Bp, H, H, 0, 0, 0}, gr + d.off[kBlk[i][0]], nullptr, 0,
+              H);
     });
     S = dx_pre_bn(dY, H, c.t(shadow_w[i]), H, H, i - 1);
     chain_mark();
@@ -1669,7 +1645,8 @@ int gm2_encode(const gm2_dims* d, int prec, const gm2_batch* batch, const float*
         ldin = H;
         Kin = H;
       }
-      const int S = gemm_to_slabs<T>(c, c.t(lo.A[2]), H, Bp, c.t(lo.sHD), H, (int)dd.L2r, B, 2 * L, H, 2 * L);
+      const int S =
+          gemm_to_slabs(c, GemmArgs<T>{c.t(lo.A[2]), H, c.t(lo.sHD), H, B, 2 * L, H, Bp, (int)dd.L2r, 0}, 2 * L);
       launch_reparam<T>(c.f(lo.slabs), S, (int64_t)Bp * 2 * L, L, params + dd.off[MUB], params + dd.off[LVB], nullptr,
                         B, Bp, c.f(lo.HD), c.t(lo.Z), dd.Lr, nullptr, 0, 0, c.f(lo.klpart), c.s);
       if (mu) HIP_OK(hipMemcpy2DAsync(mu, L * 4, c.f(lo.HD), 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
@@ -1684,37 +1661,26 @@ int gm2_encode(const gm2_dims* d, int prec, const gm2_batch* batch, const float*
 int gm2_gemm(int prec, int pk, int qk, const void* P, int64_t ldp, const void* Q, int64_t ldq, float* C, int64_t ldc,
              int64_t M, int64_t N, int64_t K, int splits, float* slab_ws, void* stream) {
   return guarded([&] {
-    auto run = [&](auto tag) {
-      using T = decltype(tag);
-      GemmArgs<T> g{(const T*)P, ldp, (const T*)Q, ldq, (int)M, (int)N, (int)K, (int)round_up(M, kTile),
-                    (int)round_up(N, kTile), 0, pk ? 1 : 0, qk ? 1 : 0};
+    // one launch into C, or split-K slabs in slab_ws column-summed into C ([S][M * ldc] as rows)
+    auto run = [&](const auto& g, bool s3) {
+      const hipStream_t s = (hipStream_t)stream;
       if (splits < 0) splits = plan_gemm(g).splits;  // the hot path's own tile / split-K plan
-      if (splits == 0 || splits == 1) {
-        launch_gemm_store<T>(g, 1, C, nullptr, 0, ldc, 0, nullptr, (hipStream_t)stream);
-      } else {
-        if (!slab_ws) throw Gm2Error("gemm: split-K needs slab_ws");
-        const int S = launch_gemm_store<T>(g, splits, slab_ws, nullptr, 0, ldc, (int64_t)M * ldc, nullptr,
-                                           (hipStream_t)stream);
-        // sum the slabs column-block-wise: treat [S][M*ldc] as rows
-        launch_colsum(slab_ws, S, M * ldc, M * ldc, C, nullptr, 0, (hipStream_t)stream);
-      }
+      if (splits > 1 && !slab_ws) throw Gm2Error("gemm: split-K needs slab_ws");
+      const int S = gemm_store(g, s3, std::max(splits, 1), splits > 1 ? slab_ws : C, nullptr, 0, ldc,
+                               splits > 1 ? M * ldc : 0, s);
+      if (splits > 1) launch_colsum(slab_ws, S, M * ldc, M * ldc, C, nullptr, 0, s);
     };
+    const int pk1 = pk ? 1 : 0, qk1 = qk ? 1 : 0;
     if (prec == GM2_F32) {
-      run(float{});
+      run(GemmArgs<float>{(const float*)P, ldp, (const float*)Q, ldq, (int)M, (int)N, (int)K, (int)round_up(M, kTile),
+                          (int)round_up(N, kTile), 0, pk1, qk1}, false);
     } else if (prec == GM2_BF16) {
-      run(bf16_t{});
+      run(GemmArgs<bf16_t>{(const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, (int)M, (int)N, (int)K,
+                           (int)round_up(M, kTile), (int)round_up(N, kTile), 0, pk1, qk1}, false);
     } else if (prec == GM2_BF16X3) {  // operands from gm2_split_operand, K the real K
       if (K <= 0 || K % 32) throw Gm2Error("gemm (bf16x3): K %lld must be a positive multiple of 32", (long long)K);
-      GemmArgs<bf16_t> g{(const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, (int)M, (int)N, (int)(2 * K),
-                         (int)round_up(M, 2 * kTile), (int)round_up(N, 2 * kTile), 0, pk ? 1 : 0, qk ? 1 : 0};
-      if (splits < 0) splits = plan_gemm(g).splits;
-      if (splits == 0 || splits == 1) {
-        launch_gemm_store_x3(g, 1, C, ldc, 0, nullptr, (hipStream_t)stream);
-      } else {
-        if (!slab_ws) throw Gm2Error("gemm: split-K needs slab_ws");
-        const int S = launch_gemm_store_x3(g, splits, slab_ws, ldc, (int64_t)M * ldc, nullptr, (hipStream_t)stream);
-        launch_colsum(slab_ws, S, M * ldc, M * ldc, C, nullptr, 0, (hipStream_t)stream);
-      }
+      run(GemmArgs<bf16_t>{(const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, (int)M, (int)N, (int)(2 * K),
+                           (int)round_up(M, 2 * kTile), (int)round_up(N, 2 * kTile), 0, pk1, qk1}, true);
     } else {
       throw Gm2Error("bad precision");
     }

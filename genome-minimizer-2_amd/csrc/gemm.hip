@@ -1875,32 +1875,10 @@ static void check_gemm(const GemmArgs<T>& g, int tile) {
   if ((g.ldp * sizeof(T)) % 16 || (g.ldq * sizeof(T)) % 16) throw Gm2Error("gemm: ld not 16-B multiple");
 }
 
-// Tile / split-K plan. Big tiles when they alone fill the chip, or when K is long enough that a
-// split-K slab round trip is cheap next to the work; otherwise the 128-tile, split only when it
-// leaves most CUs idle (and never below 8 K-steps per slice).
-// (split-K factor for the 128-tile GEMMs that alone fill the chip with one short-K tile per CU, the
-// hidden-layer GEMMs: 256 tiles, 16 K-steps: opts().small_split > 1 puts that many tiles on each
-// CU so one's loads hide behind another's MFMAs; default 1)
-
+// the tile / split-K plan (gemm_plan.hpp) under the call's GM2_OPT_SMALL_SPLIT
 template <typename T>
 GemmPlan plan_gemm(const GemmArgs<T>& g) {
-  const int nk = g.K / E<T>::KT;
-  // (the exact-fp32 path stays on the 128x128 tiles: its K-step partial sums double the accumulator
-  // registers, which the 256x256 tile's 8 waves cannot hold)
-  const int tiles_big = (sizeof(T) == 2 && g.Mp % 256 == 0 && g.Np % 256 == 0) ? (g.Mp / 256) * (g.Np / 256) : 0;
-  const int tiles_small = (g.Mp / 128) * (g.Np / 128);
-  // (up to 32 K-slices: a launch with a few tiles -- the small-batch plans, e.g. the input layer and
-  // the output layer's input gradient at batch 32 / 64: 8 tiles of 128 x 128 over K = 55,040 --
-  // fills the chip; at most 8 had left 192 CUs idle, 117 -> ~30 us each at batch 64; the split
-  // slabs are summed in slice order by their consumers, deterministic)
-  auto cap = [&](int s) { return std::max(1, std::min({s, 32, std::max(1, nk / 8)})); };
-  if (tiles_big >= 256) return {256, 1};
-  if (tiles_big > 0 && g.K >= 8192) return {256, cap((256 + tiles_big - 1) / tiles_big)};
-  if (tiles_small >= 192) {
-    const int ss = opts().small_split;
-    return {128, (ss > 1 && tiles_small < 1024 && nk >= 8) ? cap(ss) : 1};
-  }
-  return {128, cap((256 + tiles_small - 1) / tiles_small)};
+  return plan_gemm_dims((int)sizeof(T), g.Mp, g.Np, g.K, opts().small_split);
 }
 
 template <typename T>
@@ -1913,10 +1891,8 @@ static bool use_big(const GemmArgs<T>& g) {
 // (option GM2_OPT_GEMM_PP = 0, or env GM2_GEMM_PP=0 for the process defaults); both parity-tested.
 static bool pp_enabled() { return opts().gemm_pp != 0; }
 
-// waves per block (GM2_OPT_SMALL_WAVES: 4 or 8; 8: step 3.52 -> 3.46 ms, profiles/r02_ab_small_waves.txt)
-// and LDS ring depth (GM2_OPT_SMALL_STAGES: 4 or 5) of the 128x128 fp32-store GEMM tiles
-
-// call f(Cfg{}) with the 128x128 fp32-store tile configuration the options select
+// call f(Cfg{}) with the 128x128 fp32-store tile configuration the options select: waves per block
+// (GM2_OPT_SMALL_WAVES: 4 or 8; 8: step 3.52 -> 3.46 ms, profiles/r02_ab_small_waves.txt)
 // (round 6 measured a 4-wave, 2-stage form with two workgroups per CU -- GM2_OPT_SMALL_PAIR, commits
 // a952803 / 09afbbc -- neutral to slower at step level and removed it: profiles/r06_small_pair_ab.txt)
 template <typename T, class F>
@@ -1959,105 +1935,125 @@ static int device_cus() {
   return cus[dev] = std::max(n, 1);
 }
 
+// where an fp32-store launch writes: rows m < msplit to C0, the rest to C1 (null: all to C0), row
+// pitch ldc, split-K slice z at offset z * slab; bias added when non-null
+struct StoreOut {
+  float* C0;
+  float* C1;
+  int msplit;
+  int64_t ldc, slab;
+  const float* bias;
+};
+
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0, bool S3 = false>
-static void store_launch_k(const GemmArgs<T>& a, int tiles, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
-                           const float* bias, const StoreEpi& bn, hipStream_t s) {
+static void store_launch_k(const GemmArgs<T>& a, int tiles, const StoreOut& o, const StoreEpi& bn, hipStream_t s) {
   // (zero-copy rows: the index table after the staging ring -- a tile's rows, or a split's k-rows)
   constexpr int table_max = IDX == 1 ? C::BM * 4 : IDX == 2 ? kMaxIdxRows * 4 : 0;
   static_assert(C::LDS + table_max <= 160 * 1024, "LDS budget");
   const int lds = C::LDS + (IDX == 1 ? C::BM * 4 : IDX == 2 ? a.k_per_split * 4 : 0);
-  if (lds > 160 * 1024) throw Gm2Error("gemm: %d bytes of LDS", lds);
-  if (IDX == 2 && a.k_per_split > kMaxIdxRows) throw Gm2Error("zero-copy rows: %d k-rows per split", a.k_per_split);
+  if (lds > C::LDS + table_max) throw Gm2Error("gemm: %d bytes of LDS", lds);
   ensure_lds_attr((const void*)k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>, C::LDS + table_max);
-  int grid = tiles;
   StoreEpi ep = bn;
-  if (bn.ntiles) {  // capped grid: the same number of rounds on fewer CUs
-    const int cus = device_cus(), rounds = (tiles + cus - 1) / cus;
-    grid = (tiles + rounds - 1) / rounds;
-    ep.ntiles = grid < tiles ? tiles : 0;
-  }
-  hipLaunchKernelGGL((k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>), dim3(grid), dim3(C::NT), lds, s, a, C0, C1 ? C1 : C0,
-                     C1 ? msplit : (1 << 30), ldc, slab, bias, ep);
+  GridCap gc{tiles, 0};
+  if (bn.ntiles) gc = capped_grid(tiles, device_cus());  // the same number of rounds on fewer CUs
+  ep.ntiles = gc.ntiles;
+  hipLaunchKernelGGL((k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>), dim3(gc.grid), dim3(C::NT), lds, s, a, o.C0,
+                     o.C1 ? o.C1 : o.C0, o.C1 ? o.msplit : (1 << 30), o.ldc, o.slab, o.bias, ep);
 }
 
 // the specialised epilogue a 256x256 launch can take (k_gemm_store EPI): 1 = plain fp32 store,
 // 2 = transposed straight from the accumulators (env GM2_TRANS_DIRECT=1, A/B), 3 = transposed
 // through LDS, 0 = general
-static int store_epi(const GemmArgs<bf16_t>& a, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
-                     const float* bias, const StoreEpi& bn) {
+static int store_epi(const GemmArgs<bf16_t>& a, const StoreOut& o, const StoreEpi& bn) {
   static const bool trans_direct = [] {
     const char* e = std::getenv("GM2_TRANS_DIRECT");
     return e && e[0] == '1';
   }();
-  const bool aligned = ((ldc | slab) & 3) == 0 && (((uintptr_t)C0) & 15) == 0;
-  if (bias || bn.mode || (C1 && msplit < a.M)) return 0;
+  const bool aligned = ((o.ldc | o.slab) & 3) == 0 && (((uintptr_t)o.C0) & 15) == 0;
+  if (o.bias || bn.mode || (o.C1 && o.msplit < a.M)) return 0;
   if (bn.trans) return aligned ? (trans_direct ? 2 : 3) : 0;
   return 1;
 }
 
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX>
-static void store_launch_epi(const GemmArgs<T>& a, int tiles, float* C0, float* C1, int msplit, int64_t ldc,
-                             int64_t slab, const float* bias, const StoreEpi& bn, hipStream_t s) {
-  switch (store_epi(a, C0, C1, msplit, ldc, slab, bias, bn)) {
-    case 1: return store_launch_k<C, T, AK, BK, PP, IDX, 1>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
-    case 2: return store_launch_k<C, T, AK, BK, PP, IDX, 2>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
-    case 3: return store_launch_k<C, T, AK, BK, PP, IDX, 3>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
-    default: return store_launch_k<C, T, AK, BK, PP, IDX, 0>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+static void store_launch_epi(const GemmArgs<T>& a, int tiles, const StoreOut& o, const StoreEpi& bn, hipStream_t s) {
+  switch (store_epi(a, o, bn)) {
+    case 1: return store_launch_k<C, T, AK, BK, PP, IDX, 1>(a, tiles, o, bn, s);
+    case 2: return store_launch_k<C, T, AK, BK, PP, IDX, 2>(a, tiles, o, bn, s);
+    case 3: return store_launch_k<C, T, AK, BK, PP, IDX, 3>(a, tiles, o, bn, s);
+    default: return store_launch_k<C, T, AK, BK, PP, IDX, 0>(a, tiles, o, bn, s);
   }
 }
 
+// main loop, row table and epilogue of one fp32-store launch. s3 (GM2_BF16X3, 256x256 ping-pong
+// tiles, plain fp32 store): three products per K-tile over split operands in the three layouts; with
+// g.qrow (both MN-major) plain K-tiles, Q's k-rows through the row table
 template <class C, typename T, bool AK, bool BK>
-static void store_launch(const GemmArgs<T>& a, int tiles, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
-                         const float* bias, const StoreEpi& bn, hipStream_t s) {
+static void store_launch(const GemmArgs<T>& a, int tiles, const StoreOut& o, const StoreEpi& bn, bool s3,
+                         hipStream_t s) {
   if constexpr (std::is_same_v<C, Big> && sizeof(T) == 2) {
+    if (s3) {  // (launch_gemm_store_x3 has checked the ping-pong main loop is on)
+      if (a.prow) throw Gm2Error("bf16x3 GEMM: P row table not instantiated");
+      if (!a.qrow) return store_launch_k<C, T, AK, BK, true, 0, 1, true>(a, tiles, o, bn, s);
+      if constexpr (!AK && !BK) return store_launch_k<C, T, false, false, true, 2, 1, false>(a, tiles, o, bn, s);
+      throw Gm2Error("bf16x3 GEMM: row table with this layout not instantiated");
+    }
     if (a.prow || a.qrow) {  // zero-copy rows: the input layer's two GEMMs (gemm_idx_ok checked)
       if (!pp_enabled()) throw Gm2Error("zero-copy rows need the ping-pong main loop");
       if constexpr (AK && BK) {
-        if (a.prow && !a.qrow) return store_launch_epi<C, T, AK, BK, true, 1>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+        if (a.prow && !a.qrow) return store_launch_epi<C, T, AK, BK, true, 1>(a, tiles, o, bn, s);
       }
       if constexpr (AK && !BK) {
-        if (a.qrow && !a.prow) return store_launch_epi<C, T, AK, BK, true, 2>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+        if (a.qrow && !a.prow) return store_launch_epi<C, T, AK, BK, true, 2>(a, tiles, o, bn, s);
       }
       throw Gm2Error("zero-copy rows: layout not instantiated");
     }
-    if (pp_enabled()) return store_launch_epi<C, T, AK, BK, true, 0>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+    if (pp_enabled()) return store_launch_epi<C, T, AK, BK, true, 0>(a, tiles, o, bn, s);
   }
+  if (s3) throw Gm2Error("bf16x3 GEMM: bf16 256x256 tiles only");
   if (a.prow || a.qrow) throw Gm2Error("zero-copy rows: bf16 256x256 tiles only");
-  store_launch_k<C, T, AK, BK, false>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+  store_launch_k<C, T, AK, BK, false>(a, tiles, o, bn, s);
 }
 
+// one launch over the K-slices `splits` asks for (k_slices); returns the slices (= slabs) taken
 template <class C, typename T>
-static int store_impl(const GemmArgs<T>& g, int splits, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
-                      const float* bias, const StoreEpi& bn, hipStream_t s) {
+static int store_impl(const GemmArgs<T>& g, int splits, const StoreOut& o, const StoreEpi& bn, bool s3, hipStream_t s) {
   GemmArgs<T> a = g;
-  const int kt = E<T>::KT;
-  const int nkt = g.K / kt;
-  splits = std::max(1, std::min(splits, nkt));
-  a.k_per_split = (int)(round_up(nkt, splits) / splits) * kt;
-  splits = (int)((g.K + a.k_per_split - 1) / a.k_per_split);
-  const int tiles = (g.Mp / C::BM) * (g.Np / C::BN) * splits;
+  const KSlices ks = k_slices(g.K, E<T>::KT, splits);
+  if (g.qrow && !row_table_fits(g.K, E<T>::KT, splits))
+    throw Gm2Error("zero-copy rows: %d k-rows per split", ks.k_per_split);
+  if (bn.sq && ks.splits != 1) throw Gm2Error("gemm: sums of squares need one K pass");
+  a.k_per_split = ks.k_per_split;
+  const int tiles = (g.Mp / C::BM) * (g.Np / C::BN) * ks.splits;
   TimedLaunch tl(kKcGemmStore, s);
-  if (g.pk && g.qk) store_launch<C, T, true, true>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
-  else if (g.pk && !g.qk) store_launch<C, T, true, false>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
-  else if (!g.pk && !g.qk) store_launch<C, T, false, false>(a, tiles, C0, C1, msplit, ldc, slab, bias, bn, s);
+  if (g.pk && g.qk) store_launch<C, T, true, true>(a, tiles, o, bn, s3, s);
+  else if (g.pk && !g.qk) store_launch<C, T, true, false>(a, tiles, o, bn, s3, s);
+  else if (!g.pk && !g.qk) store_launch<C, T, false, false>(a, tiles, o, bn, s3, s);
   else throw Gm2Error("gemm: layout (P MN-major, Q K-major) not instantiated");
   GM2_CHECK_LAUNCH();
-  return splits;
+  return ks.splits;
+}
+
+// the big-or-small dispatch of every fp32-store launcher: 256x256 tiles (bf16 only, see
+// plan_gemm_dims) when `big`, else the 128x128 configuration the options select
+template <typename T>
+static int store_dispatch(const GemmArgs<T>& g, bool big, int splits, const StoreOut& o, const StoreEpi& ep, bool s3,
+                          hipStream_t s) {
+  if constexpr (sizeof(T) == 2) {
+    if (big) {
+      check_gemm(g, 256);
+      return store_impl<Big, T>(g, splits, o, ep, s3, s);
+    }
+  }
+  check_gemm(g, 128);
+  return small_cfg<T>([&](auto cfg) { return store_impl<decltype(cfg), T>(g, splits, o, ep, s3, s); });
 }
 
 template <typename T>
 int launch_gemm_store(const GemmArgs<T>& g, int splits, float* C0, float* C1, int msplit, int64_t ldc, int64_t slab,
                       const float* bias, hipStream_t s) {
   if (splits < 0) splits = plan_gemm(g).splits;
-  const StoreEpi none{};
-  if constexpr (sizeof(T) == 2) {  // (256x256 tiles: bf16 only, see plan_gemm)
-    if (use_big(g)) {
-      check_gemm(g, 256);
-      return store_impl<Big, T>(g, splits, C0, C1, msplit, ldc, slab, bias, none, s);
-    }
-  }
-  check_gemm(g, 128);
-  return small_cfg<T>([&](auto cfg) { return store_impl<decltype(cfg), T>(g, splits, C0, C1, msplit, ldc, slab, bias, none, s); });
+  return store_dispatch(g, use_big(g), splits, {C0, C1, msplit, ldc, slab, bias}, StoreEpi{}, false, s);
 }
 
 template <typename T>
@@ -2070,20 +2066,11 @@ bool launch_gemm_sq(const GemmArgs<T>& g, float* C, int64_t ldc, double* sq, hip
   // force_big: a one-pass 256x256-tile launch even where the plan would pick 128 tiles (a row
   // slice of a big-tile GEMM, same per-element results as the whole)
   const bool big = force_big ? (sizeof(T) == 2 && g.Mp % 256 == 0 && g.Np % 256 == 0) : use_big(g);
-  if (!force_big && plan_gemm(g).splits != 1) return false;
-  if (force_big && !big) return false;
+  if (force_big ? !big : plan_gemm(g).splits != 1) return false;
   StoreEpi ep;
   ep.sq = sq;
-  ep.ntiles = (grid_cap_bits() & 2) && !force_big;  // dWe0 bit
-  if constexpr (sizeof(T) == 2) {
-    if (big) {
-      check_gemm(g, 256);
-      store_impl<Big, T>(g, 1, C, nullptr, 0, ldc, 0, nullptr, ep, s);
-      return true;
-    }
-  }
-  check_gemm(g, 128);
-  small_cfg<T>([&](auto cfg) { return store_impl<decltype(cfg), T>(g, 1, C, nullptr, 0, ldc, 0, nullptr, ep, s); });
+  ep.ntiles = (grid_cap_bits() & 2) && !force_big;  // dWe0 bit (store_launch_k sets the count)
+  store_dispatch(g, big, 1, {C, nullptr, 0, ldc, 0, nullptr}, ep, false, s);
   return true;
 }
 
@@ -2093,37 +2080,40 @@ bool launch_gemm_trans(const GemmArgs<T>& g, float* C, int64_t ldc, hipStream_t 
   StoreEpi ep;
   ep.trans = 1;
   ep.sq = sq;
-
-  ep.ntiles = grid_cap_bits() & 1;  // dW9 bit (the launcher sets the count)
-  if constexpr (sizeof(T) == 2) {
-    if (use_big(g)) {
-      check_gemm(g, 256);
-      store_impl<Big, T>(g, 1, C, nullptr, 0, ldc, 0, nullptr, ep, s);
-      return true;
-    }
-  }
-  check_gemm(g, 128);
-  small_cfg<T>([&](auto cfg) { return store_impl<decltype(cfg), T>(g, 1, C, nullptr, 0, ldc, 0, nullptr, ep, s); });
+  ep.ntiles = grid_cap_bits() & 1;  // dW9 bit (store_launch_k sets the count)
+  store_dispatch(g, use_big(g), 1, {C, nullptr, 0, ldc, 0, nullptr}, ep, false, s);
   return true;
 }
 
 // BatchNorm statistics in the store epilogue (GM2_OPT_BN_EPILOGUE, default on): taken when the
 // plan is one pass of 128-row tiles (the statistics chunk), else the caller runs the separate pass
-
-
 template <typename T>
 bool launch_gemm_bn(const GemmArgs<T>& g, float* C, int64_t ldc, const float* bias, const StoreEpi& bn, hipStream_t s) {
   static_assert(Small::BM == kBnRowChunk, "statistics chunk = row tile");
   if (!opts().bn_epilogue) return false;
   const GemmPlan p = plan_gemm(g);
   if (p.tile != 128 || p.splits != 1 || (bn.mode && (g.N % 4 || bn.ldy % 4))) return false;
-  check_gemm(g, 128);
-  small_cfg<T>([&](auto cfg) { return store_impl<decltype(cfg), T>(g, 1, C, nullptr, 0, ldc, 0, bias, bn, s); });
+  store_dispatch(g, false, 1, {C, nullptr, 0, ldc, 0, bias}, bn, false, s);
   return true;
 }
 
+// the loss GEMM's tile: 256x256 when it fills the chip (bf16 only: the fp32 parity path stays on the
+// 128-tile, a 256-row fp32 dL image would not fit the LDS). GM2_OPT_RECON_TILE: 0 = plan,
+// 128 / 256 = force (A/B measurements)
 template <typename T>
-static bool recon_big(const GemmArgs<T>& g);
+static bool recon_big(const GemmArgs<T>& g) {
+  const int force = opts().recon_tile;
+  const bool ok = sizeof(T) == 2 && g.Mp % 256 == 0 && g.Np % 256 == 0;
+  if (force == 128) return false;
+  if (force == 256) return ok;
+  return ok && (g.Mp / 256) * (g.Np / 256) >= 128;
+}
+
+// workgroups of a launch over `tiles` tiles: all of them, or with GM2_OPT_GRID_CAP bit `bit` the
+// capped grid of the same rounds
+static GridCap grid_for(int tiles, int bit) {
+  return (grid_cap_bits() & bit) ? capped_grid(tiles, device_cus()) : GridCap{tiles, 0};
+}
 
 template <typename T>
 int gemm_recon_grid_blocks(const GemmArgs<T>& g) {
@@ -2144,16 +2134,10 @@ static void recon_impl_k(const GemmArgs<T>& g, const float* bias, const uint32_t
   if (ldx * 32 < g.Mp || (ldx & 3)) throw Gm2Error("recon: target bit rows too short");
   constexpr int lds = recon_lds_bytes<C, T>();
   static_assert(lds <= 160 * 1024, "LDS budget");
-  const int tiles = (g.Mp / C::BM) * (g.Np / C::BN);
-  int grid = tiles, ntiles = 0;
-  if (grid_cap_bits() & 4) {  // same rounds on fewer workgroups
-    const int cus = device_cus(), rounds = (tiles + cus - 1) / cus;
-    grid = (tiles + rounds - 1) / rounds;
-    ntiles = grid < tiles ? tiles : 0;
-  }
+  const GridCap gc = grid_for((g.Mp / C::BM) * (g.Np / C::BN), 4);
   auto go = [&](auto kern) {
     ensure_lds_attr((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), lds, s, g, bias, X, ldx, ntiles, scal, dL, ldd, loss_part,
+    hipLaunchKernelGGL(kern, dim3(gc.grid), dim3(C::NT), lds, s, g, bias, X, ldx, gc.ntiles, scal, dL, ldd, loss_part,
                        colpart, ldcol, xrows);
   };
   if (with_grad) go(k_gemm_recon_loss<C, T, PP, true>);
@@ -2169,19 +2153,6 @@ static void recon_impl(const GemmArgs<T>& g, const float* bias, const uint32_t* 
       return recon_impl_k<C, T, true>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
   }
   recon_impl_k<C, T, false>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
-}
-
-// the fp32 parity path stays on the 128-tile (a 256-row fp32 dL image would not fit the LDS).
-// GM2_OPT_RECON_TILE: 0 = plan (256 when it fills the chip), 128 / 256 = force (A/B measurements)
-
-
-template <typename T>
-static bool recon_big(const GemmArgs<T>& g) {
-  const int force = opts().recon_tile;
-  const bool ok = sizeof(T) == 2 && g.Mp % 256 == 0 && g.Np % 256 == 0;
-  if (force == 128) return false;
-  if (force == 256) return ok;
-  return ok && (g.Mp / 256) * (g.Np / 256) >= 128;
 }
 
 template <typename T>
@@ -2201,42 +2172,24 @@ void launch_gemm_recon_loss(const GemmArgs<T>& g, const float* bias, const uint3
 }
 
 // ---- GM2_BF16X3: the split-operand GEMMs (gm2_kernels.hpp) ----
+template <typename T>
+bool gemm_idx_ok(const GemmArgs<T>& g) {
+  if (sizeof(T) != 2 || !pp_enabled()) return false;
+  const GemmPlan p = plan_gemm<T>(g);
+  // (P rows: one 256-row table per tile; Q k-rows: a K-slice's k-rows in the table)
+  return p.tile == 256 && (!g.qrow || row_table_fits(g.K, E<T>::KT, p.splits));
+}
+
 bool gemm_x3_ok(const GemmArgs<bf16_t>& g) {
-  if (!pp_enabled() || g.Mp % 256 || g.Np % 256 || g.K % 64 || plan_gemm<bf16_t>(g).tile != 256) return false;
-  if (!g.qrow) return true;
-  const int nkt = g.K / 64, splits = std::max(1, std::min(plan_gemm<bf16_t>(g).splits, nkt));
-  return (int)(round_up(nkt, splits) / splits) * 64 <= kMaxIdxRows;
+  return g.Mp % 256 == 0 && g.Np % 256 == 0 && g.K % 64 == 0 && gemm_idx_ok<bf16_t>(g);
 }
 
 int launch_gemm_store_x3(const GemmArgs<bf16_t>& g, int splits, float* C, int64_t ldc, int64_t slab, double* sq,
                          hipStream_t s) {
   if (!pp_enabled()) throw Gm2Error("bf16x3 GEMM needs the ping-pong main loop (GM2_OPT_GEMM_PP)");
-  check_gemm(g, 256);
-  if (g.prow) throw Gm2Error("bf16x3 GEMM: P row table not instantiated");
-  GemmArgs<bf16_t> a = g;
-  const int nkt = g.K / 64;
-  splits = std::max(1, std::min(splits, nkt));
-  a.k_per_split = (int)(round_up(nkt, splits) / splits) * 64;
-  splits = (int)((g.K + a.k_per_split - 1) / a.k_per_split);
-  if (sq && splits != 1) throw Gm2Error("bf16x3 GEMM: sums of squares need one K pass");
-  const int tiles = (g.Mp / 256) * (g.Np / 256) * splits;
   StoreEpi ep;
   ep.sq = sq;
-  TimedLaunch tl(kKcGemmStore, s);
-  if (g.qrow) {  // the exact 0/1 side's k-rows duplicated through the row table: a plain K-tile per (hi | lo)
-    if (g.pk || g.qk) throw Gm2Error("bf16x3 GEMM: row table with this layout not instantiated");
-    store_launch_k<Big, bf16_t, false, false, true, 2, 1, false>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
-  } else if (g.pk && g.qk) {
-    store_launch_k<Big, bf16_t, true, true, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
-  } else if (g.pk && !g.qk) {
-    store_launch_k<Big, bf16_t, true, false, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
-  } else if (!g.pk && !g.qk) {
-    store_launch_k<Big, bf16_t, false, false, true, 0, 1, true>(a, tiles, C, nullptr, 0, ldc, slab, nullptr, ep, s);
-  } else {
-    throw Gm2Error("gemm: layout (P MN-major, Q K-major) not instantiated");
-  }
-  GM2_CHECK_LAUNCH();
-  return splits;
+  return store_dispatch(g, true, splits, {C, nullptr, 0, ldc, slab, nullptr}, ep, true, s);
 }
 
 bool gemm_recon_x3_ok(const GemmArgs<bf16_t>& g) { return pp_enabled() && g.K % 64 == 0 && recon_big<bf16_t>(g); }
@@ -2250,32 +2203,15 @@ void launch_gemm_recon_loss_x3(const GemmArgs<bf16_t>& g, const float* bias, con
     throw Gm2Error("bf16x3 recon: gcols %d, ldd %lld, target pitch %lld", gcols, (long long)ldd, (long long)ldx);
   constexpr int lds = recon_x3_lds_bytes();
   static_assert(lds <= 160 * 1024, "LDS budget");
-  const int tiles = (g.Mp / 256) * (g.Np / 256);
-  int grid = tiles, ntiles = 0;
-  if (grid_cap_bits() & 4) {
-    const int cus = device_cus(), rounds = (tiles + cus - 1) / cus;
-    grid = (tiles + rounds - 1) / rounds;
-    ntiles = grid < tiles ? tiles : 0;
-  }
+  const GridCap gc = grid_for((g.Mp / 256) * (g.Np / 256), 4);
   auto go = [&](auto kern) {
     ensure_lds_attr((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Big::NT), lds, s, g, bias, X, ldx, ntiles, scal, dL, ldd, gcols, drows,
-                       loss_part, colpart, ldcol);
+    hipLaunchKernelGGL(kern, dim3(gc.grid), dim3(Big::NT), lds, s, g, bias, X, ldx, gc.ntiles, scal, dL, ldd, gcols,
+                       drows, loss_part, colpart, ldcol);
   };
   if (with_grad) go(k_gemm_recon_loss_x3<true>);
   else go(k_gemm_recon_loss_x3<false>);
   GM2_CHECK_LAUNCH();
-}
-
-template <typename T>
-bool gemm_idx_ok(const GemmArgs<T>& g) {
-  if (sizeof(T) != 2 || !pp_enabled()) return false;
-  const GemmPlan p = plan_gemm<T>(g);
-  if (p.tile != 256) return false;
-  if (!g.qrow) return true;  // (P rows: one 256-row table per tile)
-  const int nkt = g.K / E<T>::KT, splits = std::max(1, std::min(p.splits, nkt));
-  const int kps = (int)(round_up(nkt, splits) / splits) * E<T>::KT;
-  return kps <= kMaxIdxRows;  // (Q k-rows: a split's k-rows in the table)
 }
 
 void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* mask,

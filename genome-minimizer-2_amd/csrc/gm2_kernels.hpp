@@ -9,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "gemm_plan.hpp"
 #include "gm2_common.hpp"
 
 namespace gm2 {
@@ -176,9 +177,7 @@ int gemm_recon_grid_blocks(const GemmArgs<T>& g);
 template <typename T>
 int gemm_recon_row_tiles(const GemmArgs<T>& g);
 
-struct GemmPlan {
-  int tile, splits;
-};
+// the tile / split-K plan of g under the call's options (gemm_plan.hpp plan_gemm_dims)
 template <typename T>
 GemmPlan plan_gemm(const GemmArgs<T>& g);
 // output layer GEMM computed transposed (P = W9 shadow [Gp][H], M = genes; Q = A5 [Bp][H], N =
@@ -188,8 +187,7 @@ void launch_gemm_recon_loss(const GemmArgs<T>& g, const float* bias, const uint3
                             const float* scal, T* dL, int64_t ldd, float* loss_part, float* colpart, int64_t ldcol,
                             hipStream_t s, const int32_t* xrows = nullptr);
 // whether a GEMM with zero-copy rows (GemmArgs.prow / qrow) runs as planned: bf16, ping-pong main
-// loop on, the 256x256 plan (and for qrow at most kMaxIdxRows k-rows per split)
-constexpr int kMaxIdxRows = 8192;
+// loop on, the 256x256 plan (and for qrow at most kMaxIdxRows k-rows per split: row_table_fits)
 template <typename T>
 bool gemm_idx_ok(const GemmArgs<T>& g);
 // ---- GM2_BF16X3 (gm2.h): GEMMs over operands in the split layout of launch_split_kmajor /

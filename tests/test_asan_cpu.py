@@ -6,8 +6,9 @@ tools/asan/host_asan.cpp into one executable. It needs no GPU: it sweeps the wor
 7,200 (dims, precision) cases through gm2_debug_check_layout (every region 256-B aligned, disjoint,
 inside the total, every named offset a region start), the resident-operand layouts and gradient
 buckets, every option key against valid and invalid values (a refused value leaves the option
-unchanged), the per-workspace entry points on unknown state, and the error paths of the compute
-entry points. Exit 0 = all checks passed and ASan reported nothing.
+unchanged), the per-workspace entry points on unknown state, the GEMM launch geometry of
+csrc/gemm_plan.hpp against a table of expected values (tile / split-K plans, K-slices, capped grids,
+the row-table limit, the slab-capacity rules), and the error paths of the compute entry points. Exit 0 = all checks passed and ASan reported nothing.
 
 The device side of the same GM2_DEBUG build (bounds checks of the gather rows, zero-copy row tables,
 loss target rows, mask positions and CSR spans) runs on the GPU: tests/test_gpu_debug_build.py."""

@@ -49,6 +49,9 @@ def bn_epi(request):
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("M,N,K,splits", [(128, 128, 64, 1), (200, 300, 192, 1), (256, 1024, 1024, 1),
                                           (300, 256, 4096, 4), (1000, 130, 320, 1), (2048, 1024, 512, 1),
+                                          # fewer slabs come back than asked for (bf16: 9 K-tiles in 4
+                                          # slices = 3 + 3 + 3)
+                                          (128, 128, 576, 4),
                                           # 256x256 ping-pong tiles: >= 256 tiles (nk = 1, 3), and the
                                           # long-K plan (big tiles + 8 split-K slices)
                                           (4000, 4096, 64, 1), (4096, 4000, 192, 1), (512, 512, 8192, -1)])

@@ -4,7 +4,8 @@
 // needs no GPU and launches no kernel: it drives the C-ABI entry points whose work is host
 // arithmetic -- dims and parameter offsets, the workspace layout (gm2_debug_check_layout: alignment,
 // overlap, bounds of every region), resident-operand layouts, gradient buckets, the option tables
-// (every key, valid and invalid values, process defaults vs per-workspace state), and the error
+// (every key, valid and invalid values, process defaults vs per-workspace state), the GEMM launch
+// geometry (csrc/gemm_plan.hpp: plans, K-slices, capped grids, slab capacity), and the error
 // paths of every entry point given null / inconsistent arguments or an unknown workspace -- so any
 // heap / stack / global overflow or use-after-free in that code aborts the run with an ASan report.
 // Exit code 0 = every check passed and ASan saw nothing. tests/test_asan_cpu.py runs it.
@@ -16,6 +17,7 @@
 
 #include "../../include/gm2.h"
 #include "../../include/gm2_debug.h"
+#include "gm2_kernels.hpp"  // csrc/: plan_gemm<T> and, through gemm_plan.hpp, the launch-geometry rules
 
 static int g_fail = 0;
 #define CHECK(c, ...)                                     \
@@ -207,10 +209,93 @@ static void error_paths() {
   (void)flags;
 }
 
+// csrc/gemm_plan.hpp: every rule of the GEMM launch geometry against expected values (derived by
+// hand from the rules as the launchers stated them before the header existed)
+static void gemm_geometry() {
+  using namespace gm2;
+  // plan_gemm under the default options: the pure rule and the launchers' wrapper
+  struct PlanRow {
+    int esize, Mp, Np, K, tile, splits;
+  };
+  const PlanRow plans[] = {{2, 1024, 55040, 1024, 256, 1},  {2, 55040, 1024, 1024, 256, 1},
+                           {2, 1024, 1024, 55040, 256, 16}, {4, 1024, 1024, 55040, 128, 4},
+                           {2, 1024, 1024, 1024, 128, 2},   {4, 1024, 1024, 1024, 128, 4},
+                           {2, 128, 1024, 55040, 128, 32},  {2, 2048, 1024, 1024, 128, 2},
+                           {2, 4096, 1024, 1024, 128, 1}};
+  for (const PlanRow& r : plans) {
+    const GemmPlan p = plan_gemm_dims(r.esize, r.Mp, r.Np, r.K, 1);
+    CHECK(p.tile == r.tile && p.splits == r.splits, "plan_gemm_dims(%d; %d, %d, %d) = {%d, %d}, expected {%d, %d}",
+          r.esize, r.Mp, r.Np, r.K, p.tile, p.splits, r.tile, r.splits);
+    GemmPlan w;
+    if (r.esize == 2) {
+      GemmArgs<bf16_t> g{nullptr, 0, nullptr, 0, r.Mp, r.Np, r.K, r.Mp, r.Np, 0};
+      w = plan_gemm<bf16_t>(g);
+    } else {
+      GemmArgs<float> g{nullptr, 0, nullptr, 0, r.Mp, r.Np, r.K, r.Mp, r.Np, 0};
+      w = plan_gemm<float>(g);
+    }
+    CHECK(w.tile == r.tile && w.splits == r.splits, "plan_gemm<%d B>(%d, %d, %d) = {%d, %d}, expected {%d, %d}",
+          r.esize, r.Mp, r.Np, r.K, w.tile, w.splits, r.tile, r.splits);
+  }
+  // GM2_OPT_SMALL_SPLIT reaches the chip-filling short-K 128-tile plans only
+  CHECK(plan_gemm_dims(2, 4096, 1024, 1024, 2).splits == 2 && plan_gemm_dims(2, 1024, 55040, 1024, 2).splits == 1,
+        "small_split");
+  struct SliceRow {
+    int K, kt, want, kps, splits;
+  };
+  const SliceRow slices[] = {{55040, 64, 16, 3456, 16}, {55040, 64, 32, 1728, 32}, {55040, 32, 4, 13760, 4},
+                             {2112, 64, 3, 704, 3},     {576, 64, 4, 192, 3},      {576, 32, 4, 160, 4},
+                             {64, 64, 8, 64, 1}};
+  for (const SliceRow& r : slices) {
+    const KSlices k = k_slices(r.K, r.kt, r.want);
+    CHECK(k.k_per_split == r.kps && k.splits == r.splits, "k_slices(%d, %d, %d) = {%d, %d}, expected {%d, %d}", r.K,
+          r.kt, r.want, k.k_per_split, k.splits, r.kps, r.splits);
+    // every slice whole K-tiles, together covering K, the last one not empty
+    CHECK(k.k_per_split % r.kt == 0 && (int64_t)k.k_per_split * k.splits >= r.K &&
+              (int64_t)k.k_per_split * (k.splits - 1) < r.K && k.splits <= std::max(r.want, 1),
+          "k_slices(%d, %d, %d) does not cover K", r.K, r.kt, r.want);
+  }
+  const int grids[][4] = {{860, 256, 215, 860}, {256, 256, 256, 0}, {300, 256, 150, 300}, {100, 256, 100, 0}};
+  for (const auto& r : grids) {
+    const GridCap c = capped_grid(r[0], r[1]);
+    CHECK(c.grid == r[2] && c.ntiles == r[3], "capped_grid(%d, %d) = {%d, %d}, expected {%d, %d}", r[0], r[1], c.grid,
+          c.ntiles, r[2], r[3]);
+  }
+  static_assert(kMaxIdxRows == 8192, "the row-table cases below sit at this limit");
+  CHECK(row_table_fits(8192, 64, 1), "row table: exactly kMaxIdxRows k-rows fit");
+  CHECK(!row_table_fits(8256, 64, 1), "row table: one K-tile past kMaxIdxRows does not fit");
+  CHECK(row_table_fits(16384, 64, 2), "row table: two slices of kMaxIdxRows fit");
+  // slab capacity, into slabs: padded-row slabs, the plan's count clamped, none fitting an error
+  const int64_t padded = slab_elems_padded(1024, 1024);
+  CHECK(padded == (int64_t)1 << 20, "padded slab");
+  CHECK(splits_into_slabs(16, padded, (int64_t)64 << 20) == 16, "into slabs, under capacity");
+  CHECK(splits_into_slabs(16, padded, 16 * padded) == 16, "into slabs, at capacity");
+  CHECK(splits_into_slabs(16, padded, 4 * padded + 5) == 4, "into slabs, over capacity: clamped");
+  bool threw = false;
+  try {
+    splits_into_slabs(16, padded, padded - 1);
+  } catch (const std::exception& e) {
+    threw = std::strstr(e.what(), "slab capacity exceeded") != nullptr;
+  }
+  CHECK(threw, "into slabs, not one slab fits: an error");
+  // into C: dense slabs (M x N rounded up to 4); over capacity the plain GEMMs take one pass, the
+  // bf16x3 ones the slices that fit
+  const int64_t dense = slab_elems_dense(999, 1001);
+  CHECK(dense == 1000000, "dense slab");
+  for (bool shrink : {false, true}) {
+    CHECK(splits_into_c(16, dense, 16 * dense, shrink) == 16, "into C, at capacity (shrink %d)", (int)shrink);
+    CHECK(splits_into_c(1, dense, 0, shrink) == 1, "into C, one pass needs no scratch (shrink %d)", (int)shrink);
+  }
+  CHECK(splits_into_c(16, dense, 16 * dense - 1, false) == 1, "into C, over capacity, plain: one pass");
+  CHECK(splits_into_c(16, dense, 16 * dense - 1, true) == 15, "into C, over capacity, bf16x3: the slices that fit");
+  CHECK(splits_into_c(16, dense, dense - 1, true) == 1, "into C, no slab fits, bf16x3: one pass");
+}
+
 int main() {
   CHECK(gm2_abi_version() == GM2_ABI_VERSION, "abi version");
   dims_and_layouts();
   options();
+  gemm_geometry();
   error_paths();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
