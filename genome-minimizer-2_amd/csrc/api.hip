@@ -1584,6 +1584,47 @@ int gm2_mask_compact(const uint8_t* bits, int64_t n, int64_t ld_bits, const uint
   });
 }
 
+namespace {
+// one operand of the bit-row cross products: n rows of pitch ld, 16-B aligned, covering G bits
+void check_bit_rows(const char* what, const char* name, const uint8_t* p, int64_t n, int64_t ld, int64_t G) {
+  if (n < 0) throw Gm2Error("%s: negative row count of %s (%lld)", what, name, (long long)n);
+  if (ld <= 0 || (ld & 15) || ld * 8 < G)
+    throw Gm2Error("%s: pitch of %s (%lld) must be a multiple of 16 bytes covering G = %lld bits", what, name,
+                   (long long)ld, (long long)G);
+  if ((uintptr_t)p & 15) throw Gm2Error("%s: rows of %s must be 16-B aligned", what, name);
+  if (n && !p) throw Gm2Error("%s: null %s", what, name);
+}
+}  // namespace
+
+int gm2_mask_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b, int64_t nb, int64_t ldb, int64_t G,
+                     int32_t* out, int64_t ldo, void* stream) {
+  return guarded([&] {
+    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_cooccur: G %lld outside [1, 2^31)", (long long)G);
+    check_bit_rows("mask_cooccur", "a", a, na, lda, G);
+    check_bit_rows("mask_cooccur", "b", b, nb, ldb, G);
+    if (ldo < nb) throw Gm2Error("mask_cooccur: ldo %lld < nb %lld", (long long)ldo, (long long)nb);
+    if ((uintptr_t)out & 3) throw Gm2Error("mask_cooccur: out must be 4-B aligned");
+    if (na == 0 || nb == 0) return;
+    if (!out) throw Gm2Error("mask_cooccur: null out");
+    launch_bit_cooccur(a, na, lda, b, nb, ldb, G, out, ldo, (hipStream_t)stream);
+  });
+}
+
+int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr, int64_t G,
+                     int64_t* best, void* stream) {
+  return guarded([&] {
+    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_nearest: G %lld outside [1, 2^31)", (long long)G);
+    check_bit_rows("mask_nearest", "q", q, nq, ldq, G);
+    check_bit_rows("mask_nearest", "ref", ref, nr, ldr, G);
+    if (nr == 0) throw Gm2Error("mask_nearest: no reference rows (nr = 0)");
+    if (nr > 0x7fffffff) throw Gm2Error("mask_nearest: nr %lld does not fit the 32-bit index", (long long)nr);
+    if ((uintptr_t)best & 7) throw Gm2Error("mask_nearest: best must be 8-B aligned");
+    if (nq == 0) return;
+    if (!best) throw Gm2Error("mask_nearest: null best");
+    launch_bit_nearest(q, nq, ldq, ref, nr, ldr, G, best, (hipStream_t)stream);
+  });
+}
+
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {

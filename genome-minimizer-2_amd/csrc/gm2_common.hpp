@@ -69,6 +69,7 @@ enum DebugBit : unsigned {
   kDbgReconRows = 32u,     // loss epilogue: target-bit row outside [0, idx_lim)
   kDbgTile = 64u,          // a GEMM tile origin outside the padded operand extents
   kDbgBandBlock = 128u,    // band-list overflow: a flagged 256 x 256 block outside the block grid
+  kDbgBitRows = 256u,      // k_bit_cooccur / k_bit_nearest: a store outside out / a winner outside [0, nr)
 };
 #ifdef GM2_DEBUG
 namespace {

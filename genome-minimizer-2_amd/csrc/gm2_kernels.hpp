@@ -431,6 +431,13 @@ void launch_row_offsets(const uint8_t* bits, int64_t n, int64_t ldb, const uint8
                         hipStream_t s);
 void launch_compact(const uint8_t* bits, int64_t n, int64_t ldb, const uint8_t* keep, const int64_t* offsets,
                     int32_t* idx, hipStream_t s);
+// bit-row cross products over the rows' first roundup(G, 128) / 8 bytes (rows 16-B aligned, bits
+// beyond G zero): out[i][j] = popcount(a_i AND b_j) (int32, pitch ldo, columns >= nb untouched);
+// best[i] = min_j (popcount(q_i XOR r_j) << 32 | j), filled with the identity (2^63 - 1) first
+void launch_bit_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b, int64_t nb, int64_t ldb, int64_t G,
+                        int32_t* out, int64_t ldo, hipStream_t s);
+void launch_bit_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr, int64_t G,
+                        int64_t* best, hipStream_t s);
 
 // parameter tensor table for the multi-tensor optimizer / shadow kernels
 struct TensorDesc {

@@ -3,10 +3,13 @@
 //     present, a gene counting when ANY of its column positions is set;
 //   * masks_to_gene_lists (explore_data/binary_converter.py:19-76): per sample, the ascending
 //     column indices of the set genes (duplicate gene names dropped through a keep mask), as a
-//     CSR (row offsets = exclusive scan of row popcounts, then a wave-parallel compaction).
+//     CSR (row offsets = exclusive scan of row popcounts, then a wave-parallel compaction);
+//   * the integer cross products of two sets of rows (no reference kernel: its PCA of the strains,
+//     explore_data/data_exploration.py:394-420, unpacks to float64): popcount(a AND b), the Gram
+//     matrix of 0/1 rows, and the nearest row by popcount(a XOR b). VALU-bound, LDS-tiled.
 // Mask rows are numpy packbits(bitorder='little') bytes: bit (g & 7) of byte g / 8 = gene g,
-// row pitch ld_bits (multiple of 16 bytes), bits beyond G zero. HBM-bound integer work: every
-// kernel streams each mask row once with 16-byte (or 4-byte word) loads.
+// row pitch ld_bits (multiple of 16 bytes), bits beyond G zero. The first two are HBM-bound integer
+// work: their kernels stream each mask row once with 16-byte (or 4-byte word) loads.
 #include "../../include/gm2.h"
 #include "gm2_common.hpp"
 #include "gm2_kernels.hpp"
@@ -202,7 +205,193 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ bit
   }
 }
 
+// ---- bit-row cross products: out[i][j] = popcount(a_i OP b_j), OP = AND (co-occurrence, the Gram
+// matrix of 0/1 rows) or XOR (Hamming distance) ----
+// A workgroup of 256 lanes owns a 64 x 64 tile of (A row, B row) pairs and walks the rows' bytes in
+// chunks of kBgChunk: both 64-row tiles of the chunk are staged in LDS with 16-byte global loads (the
+// next chunk's loads are in flight while this one is consumed), rows beyond na / nb and bytes beyond
+// the row's kb zero-filled there. Lane (ty = t / 16, tx = t % 16) accumulates the 4 x 4 block of pairs
+// (A rows ty + 16 r, B rows tx + 16 c): per 16 bytes of the rows 8 ds_read_b128 feed 64
+// (v_and | v_xor) + v_bcnt_u32_b32 pairs, i.e. 16 x 128 gene pairs. LDS rows are pitched kBgChunk + 16
+// bytes = an odd number of 16-byte slots, so the 16 B rows a ds_read_b128 lane group reads sit on 16
+// different slots of the 256-byte bank row, and its 2 A rows (every other lane a broadcast) on two.
+constexpr int kBgTile = 64;
+constexpr int kBgChunk = 128;             // bytes of each row per LDS stage (1024 genes)
+constexpr int kBgPitch = kBgChunk + 16;   // 9 slots of 16 bytes
+constexpr int kBgPieces = kBgTile * (kBgChunk / 16) / 256;  // 16-byte pieces per lane per operand
+
+struct BitTile {
+  uint4 a[kBgPieces], b[kBgPieces];
+};
+
+// the chunk at byte k0 of both tiles -> registers (zero beyond the rows / the row bytes)
+__device__ __forceinline__ void bg_load(BitTile& t, const uint8_t* __restrict__ A, int64_t na, int64_t lda, int64_t i0,
+                                        const uint8_t* __restrict__ B, int64_t nb, int64_t ldb, int64_t j0,
+                                        int64_t k0, int64_t kb) {
+#pragma unroll
+  for (int p = 0; p < kBgPieces; ++p) {
+    const int piece = threadIdx.x + p * 256, row = piece >> 3;
+    const int64_t k = k0 + (piece & 7) * 16;
+    t.a[p] = t.b[p] = make_uint4(0u, 0u, 0u, 0u);
+    if (i0 + row < na && k < kb) t.a[p] = *(const uint4*)(A + (i0 + row) * lda + k);
+    if (j0 + row < nb && k < kb) t.b[p] = *(const uint4*)(B + (j0 + row) * ldb + k);
+  }
+}
+
+__device__ __forceinline__ void bg_stage(const BitTile& t, uint8_t* la, uint8_t* lb) {
+#pragma unroll
+  for (int p = 0; p < kBgPieces; ++p) {
+    const int piece = threadIdx.x + p * 256, o = (piece >> 3) * kBgPitch + (piece & 7) * 16;
+    *(uint4*)(la + o) = t.a[p];
+    *(uint4*)(lb + o) = t.b[p];
+  }
+}
+
+template <bool kXor>
+__device__ __forceinline__ int bg_pop(const uint4& x, const uint4& y, int acc) {
+  if (kXor) {
+    acc += __builtin_popcount(x.x ^ y.x);
+    acc += __builtin_popcount(x.y ^ y.y);
+    acc += __builtin_popcount(x.z ^ y.z);
+    acc += __builtin_popcount(x.w ^ y.w);
+  } else {
+    acc += __builtin_popcount(x.x & y.x);
+    acc += __builtin_popcount(x.y & y.y);
+    acc += __builtin_popcount(x.z & y.z);
+    acc += __builtin_popcount(x.w & y.w);
+  }
+  return acc;
+}
+
+// acc[r][c] = popcount(A[i0 + ty + 16 r] OP B[j0 + tx + 16 c]) over the rows' first kb bytes
+template <bool kXor>
+__device__ __forceinline__ void bg_tile(const uint8_t* __restrict__ A, int64_t na, int64_t lda, int64_t i0,
+                                        const uint8_t* __restrict__ B, int64_t nb, int64_t ldb, int64_t j0, int64_t kb,
+                                        int (&acc)[4][4]) {
+  __shared__ __attribute__((aligned(16))) uint8_t la[kBgTile * kBgPitch];
+  __shared__ __attribute__((aligned(16))) uint8_t lb[kBgTile * kBgPitch];
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[r][c] = 0;
+  BitTile t;
+  bg_load(t, A, na, lda, i0, B, nb, ldb, j0, 0, kb);
+  for (int64_t k0 = 0; k0 < kb; k0 += kBgChunk) {
+    __syncthreads();  // (the previous chunk's reads are done)
+    bg_stage(t, la, lb);
+    __syncthreads();
+    if (k0 + kBgChunk < kb) bg_load(t, A, na, lda, i0, B, nb, ldb, j0, k0 + kBgChunk, kb);
+#pragma unroll
+    for (int s = 0; s < kBgChunk / 16; ++s) {
+      uint4 x[4], y[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x[r] = *(const uint4*)(la + (ty + 16 * r) * kBgPitch + s * 16);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) y[c] = *(const uint4*)(lb + (tx + 16 * c) * kBgPitch + s * 16);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = bg_pop<kXor>(x[r], y[c], acc[r][c]);
+    }
+  }
+}
+
+// tiles in a 1-D grid, B tiles fastest: neighbouring workgroups share their A tile and walk B, which
+// (7,512 F4 rows = 52 MB) stays in the last-level cache
+__global__ __launch_bounds__(256) void k_bit_cooccur(const uint8_t* __restrict__ A, int64_t na, int64_t lda,
+                                                   const uint8_t* __restrict__ B, int64_t nb, int64_t ldb, int64_t kb,
+                                                   int32_t* __restrict__ out, int64_t ldo, int tiles_b) {
+  const int64_t i0 = (int64_t)(blockIdx.x / tiles_b) * kBgTile, j0 = (int64_t)(blockIdx.x % tiles_b) * kBgTile;
+  int acc[4][4];
+  bg_tile<false>(A, na, lda, i0, B, nb, ldb, j0, kb, acc);
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t i = i0 + ty + 16 * r;
+    if (i >= na) continue;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t j = j0 + tx + 16 * c;
+      if (j >= nb) continue;
+      GM2_DBG(i >= 0 && j >= 0 && j < ldo && i * ldo + j < na * ldo, kDbgBitRows);
+      out[i * ldo + j] = acc[r][c];
+    }
+  }
+}
+
+// best[i] = min over the tile's reference rows j of (distance << 32 | j), merged into global memory
+// with a 64-bit atomic min: the keys are non-negative and unique per (distance, j), so the minimum
+// is the nearest row, the lowest index among ties, whatever order the tiles arrive in
+__global__ __launch_bounds__(256) void k_bit_nearest(const uint8_t* __restrict__ Q, int64_t nq, int64_t ldq,
+                                                   const uint8_t* __restrict__ R, int64_t nr, int64_t ldr, int64_t kb,
+                                                   unsigned long long* __restrict__ best, int tiles_r) {
+  const int64_t i0 = (int64_t)(blockIdx.x / tiles_r) * kBgTile, j0 = (int64_t)(blockIdx.x % tiles_r) * kBgTile;
+  int acc[4][4];
+  bg_tile<true>(Q, nq, ldq, i0, R, nr, ldr, j0, kb, acc);
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    unsigned long long key = ~0ull >> 1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t j = j0 + tx + 16 * c;
+      const unsigned long long k = ((unsigned long long)(unsigned)acc[r][c] << 32) | (unsigned long long)j;
+      if (j < nr && k < key) key = k;
+    }
+    // (the 16 lanes of one ty are 16 neighbouring lanes of a wave)
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) {
+      const unsigned long long v = __shfl_xor(key, o, 64);
+      key = v < key ? v : key;
+    }
+    const int64_t i = i0 + ty + 16 * r;
+    if (tx == 0 && i < nq) {
+      GM2_DBG(i >= 0 && (key & 0xffffffffull) < (unsigned long long)nr, kDbgBitRows);
+      atomicMin(&best[i], key);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fill_u64(unsigned long long* __restrict__ p, int64_t n, unsigned long long v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// 1-D grid of ta x tb tiles
+unsigned bit_grid(int64_t ra, int64_t rb, int* tiles_b) {
+  const int64_t ta = (ra + kBgTile - 1) / kBgTile, tb = (rb + kBgTile - 1) / kBgTile;
+  if (tb > 0x7fffffff || ta * tb > 0x7fffffff)
+    throw Gm2Error("bit rows: %lld x %lld rows are more tiles than one launch holds", (long long)ra, (long long)rb);
+  *tiles_b = (int)tb;
+  return (unsigned)(ta * tb);
+}
 }  // namespace
+
+void launch_bit_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b, int64_t nb, int64_t ldb, int64_t G,
+                        int32_t* out, int64_t ldo, hipStream_t s) {
+  if (na <= 0 || nb <= 0) return;
+  int tb;
+  const unsigned grid = bit_grid(na, nb, &tb);
+  const int64_t kb = (G + 127) / 128 * 16;
+  hipLaunchKernelGGL(k_bit_cooccur, dim3(grid), dim3(256), 0, s, a, na, lda, b, nb, ldb, kb, out, ldo, tb);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_bit_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr, int64_t G,
+                        int64_t* best, hipStream_t s) {
+  if (nq <= 0) return;
+  int tr;
+  const unsigned grid = bit_grid(nq, nr, &tr);
+  // the identity of the min: all ones in the low 63 bits
+  hipLaunchKernelGGL(k_fill_u64, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (unsigned long long*)best, nq,
+                     ~0ull >> 1);
+  GM2_CHECK_LAUNCH();
+  const int64_t kb = (G + 127) / 128 * 16;
+  hipLaunchKernelGGL(k_bit_nearest, dim3(grid), dim3(256), 0, s, q, nq, ldq, ref, nr, ldr, kb,
+                     (unsigned long long*)best, tr);
+  GM2_CHECK_LAUNCH();
+}
 
 void launch_count_groups(const uint8_t* bits, int64_t n, int64_t ldb, const int32_t* goff, int64_t ngroups,
                          const int32_t* pos, int32_t* counts, hipStream_t s) {

@@ -35,6 +35,19 @@ def essential_groups(essential_gene_positions, G):
     return np.asarray(offs, dtype=np.int32), np.asarray(pos, dtype=np.int32)
 
 
+def pack_rows(rows):
+    """Device u8 0/1 rows [n, ld] (ld a multiple of 128, pad columns zero) -> packed rows [n, ld / 8]."""
+    n, ld = rows.shape
+    if ld % 128:
+        raise ValueError("pack_rows: the row length must be a multiple of 128")
+    w = (1 << torch.arange(8, device=rows.device, dtype=torch.int32))
+    bits = torch.empty(n, ld // 8, dtype=torch.uint8, device=rows.device)
+    for r0 in range(0, n, 1024):
+        r = rows[r0:r0 + 1024]
+        bits[r0:r0 + 1024] = (r.reshape(r.shape[0], -1, 8).to(torch.int32) * w).sum(-1).to(torch.uint8)
+    return bits
+
+
 class PackedMasks:
     """n x G packed masks on the device (a [n, ld] uint8 tensor)."""
 
@@ -60,6 +73,35 @@ class PackedMasks:
         packed[:, : (G + 7) // 8] = np.packbits(m >= threshold, axis=1, bitorder="little")
         dev = device or torch.device("cuda", torch.cuda.current_device())
         return PackedMasks(torch.from_numpy(packed).to(dev), G)
+
+    @staticmethod
+    def from_resident(matrix):
+        """The rows of a gm2.data.ResidentMatrix packed: the target bits of its GEMM operands when
+        they are already built (the same bytes), else its u8 rows packed once on the device."""
+        n, G = matrix.n, matrix.G
+        for ops in matrix.__dict__.get("_operands", {}).values():
+            return PackedMasks(ops.bits[:n].view(torch.uint8), G)
+        return PackedMasks(pack_rows(matrix.data[:n]), G)
+
+    def cooccurrence(self, other=None):
+        """popcount(row_i AND other_j) for every pair -> device int32 [n, m] (other None: this set
+        with itself, the Gram matrix X X^T of the 0/1 rows)."""
+        o = self if other is None else other
+        if o.G != self.G:
+            raise ValueError(f"cooccurrence: {self.G} genes against {o.G}")
+        out = torch.empty(self.n, o.n, dtype=torch.int32, device=self.bits.device)
+        native.mask_cooccur(self.bits, self.n, self.ld, o.bits, o.n, o.ld, self.G, out, o.n)
+        return out
+
+    def nearest(self, other):
+        """For every row the nearest row of `other` by Hamming distance, ties to the lowest index ->
+        (hamming int64 numpy [n], index int64 numpy [n]); no n x m matrix is formed."""
+        if other.G != self.G:
+            raise ValueError(f"nearest: {self.G} genes against {other.G}")
+        best = torch.empty(self.n, dtype=torch.int64, device=self.bits.device)
+        native.mask_nearest(self.bits, self.n, self.ld, other.bits, other.n, other.ld, self.G, best)
+        key = best.cpu().numpy()
+        return key >> 32, key & 0xFFFFFFFF
 
     def to_host(self):
         """numpy packbits rows [n, ceil(G/8)] (bitorder 'little')."""

@@ -37,7 +37,8 @@ EXPORTS = ["gm2_last_error", "gm2_abi_version", "gm2_param_count", "gm2_param_of
            "gm2_workspace_set_collective", "gm2_workspace_join",
            "gm2_resident_layout", "gm2_resident_build",
            "gm2_timing_begin", "gm2_timing_end", "gm2_timing_class", "gm2_workspace_stat",
-           "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand"]
+           "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand",
+           "gm2_mask_cooccur", "gm2_mask_nearest"]
 ABI_VERSION = 6
 KC_RECON_LOSS, KC_GEMM_STORE, KC_MASK, KC_ADAM = 1, 2, 4, 8
 OPT_GEMM_PP, OPT_SIDE_STREAM, OPT_RECON_TILE, OPT_SMALL_SPLIT, OPT_BN_EPILOGUE, OPT_SMALL_WAVES = 1, 2, 3, 4, 5, 6
@@ -112,6 +113,8 @@ def lib():
         "gm2_mask_count_groups": (C.c_int, [vp, i64, i64, vp, i64, vp, vp, vp]),
         "gm2_mask_row_offsets": (C.c_int, [vp, i64, i64, vp, vp, vp]),
         "gm2_mask_compact": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),
+        "gm2_mask_cooccur": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, vp, i64, vp]),
+        "gm2_mask_nearest": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, vp, vp]),
         "gm2_recon_counts": (C.c_int, [dp, i32, C.POINTER(Batch), vp, vp, C.c_float, vp, vp, vp]),
         "gm2_gemm": (C.c_int, [i32, i32, i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, vp]),
         "gm2_grad_bucket_bounds": (C.c_int, [dp, C.POINTER(C.c_int64)]),
@@ -376,6 +379,18 @@ def mask_row_offsets(bits, n, ld_bits, keep_bits, offsets):
 def mask_compact(bits, n, ld_bits, keep_bits, offsets, indices):
     check(lib().gm2_mask_compact(ptr(bits), int(n), int(ld_bits), ptr(keep_bits), ptr(offsets), ptr(indices),
                                  stream()), "gm2_mask_compact")
+
+
+def mask_cooccur(a, na, lda, b, nb, ldb, G, out, ldo):
+    """out[i][j] = popcount(a_i AND b_j) (int32, pitch ldo) over packed rows (gm2_mask_cooccur)."""
+    check(lib().gm2_mask_cooccur(ptr(a), int(na), int(lda), ptr(b), int(nb), int(ldb), int(G), ptr(out), int(ldo),
+                                 stream()), "gm2_mask_cooccur")
+
+
+def mask_nearest(q, nq, ldq, ref, nr, ldr, G, best):
+    """best[i] = min_j (popcount(q_i XOR ref_j) << 32 | j) (int64) over packed rows (gm2_mask_nearest)."""
+    check(lib().gm2_mask_nearest(ptr(q), int(nq), int(ldq), ptr(ref), int(nr), int(ldr), int(G), ptr(best), stream()),
+          "gm2_mask_nearest")
 
 
 def recon_counts(ws: Workspace, batch: Batch, params, bn, threshold, counts):

@@ -233,6 +233,22 @@ int gm2_mask_row_offsets(const uint8_t* bits, int64_t n, int64_t ld_bits, const 
 int gm2_mask_compact(const uint8_t* bits, int64_t n, int64_t ld_bits, const uint8_t* keep_bits, const int64_t* offsets,
                      int32_t* indices, void* stream);
 
+/* (ABI 6, additive) Integer cross products of two sets of packed rows (the layout above; the 32-bit
+ * words of gm2_resident_build's resident_bits have the same bytes). Each reads the first
+ * roundup(G, 128) / 8 bytes of every row; the pitches lda / ldb (multiples of 16 covering G bits)
+ * may differ, rows are 16-B aligned, bits beyond G zero. Stream-ordered, no allocation.
+ *   co-occurrence: out[i * ldo + j] = popcount(a_i AND b_j), int32, i < na, j < nb, ldo >= nb (the
+ *     columns >= nb of out are not written); a == b allowed: the Gram matrix X X^T of 0/1 rows.
+ *   nearest: best[i] = min over j < nr of ((int64)popcount(q_i XOR ref_j) << 32 | j): the Hamming
+ *     distance to the nearest reference row in the high word, its index (the lowest among ties) in
+ *     the low word. The call fills best with the identity first; no nq x nr matrix exists.
+ * Return < 0 (see the last-error message) on a negative count, G < 1, a bad pitch or alignment,
+ * ldo < nb, nr == 0; zero rows on either side of the product return 0 without a launch. */
+int gm2_mask_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b, int64_t nb, int64_t ldb,
+                     int64_t G, int32_t* out, int64_t ldo, void* stream);
+int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr,
+                     int64_t G, int64_t* best, void* stream);
+
 /* calculate_reconstruction_metrics (training/evaluation/metrics.py:19-64) without materialising the
  * reconstruction: eval-mode model(x) of `batch` (eps given: the reference samples z there too), then
  * per strain counts[i] = (TP, FP, FN) of (recon > threshold) against the strain's genes. */

@@ -31,6 +31,10 @@ float64 via `.astype(float)`, main.py:369-371 / extras.py:200-201; uint8 keeps 1
 memory; bits = numpy packbits(bitorder='little') rows, 1/64 of float64, accepted by convert-samples),
 --no-csv to skip the genes x samples CSV. Sampling keeps the masks packed on the GPU: genome sizes
 and essential-gene counts are computed there (gm2/masks.py) and only the packed rows cross PCIe.
+--nearest-strains / --pca (sample mode, both off by default) compare the sampled genomes with the
+dataset's strains on the packed rows (gm2_mask_nearest / gm2_mask_cooccur, gm2/pca.py): the nearest
+strain of every sample by Hamming distance, and the PCA of the strains (the reference's Figure 2a)
+with the samples projected onto its axes.
 """
 import argparse
 import os
@@ -65,6 +69,10 @@ def parse_arguments(argv=None):
                    help="torchrun / DDP only: train-mode BatchNorm over the global batch (SyncBN)")
     p.add_argument("--mask-dtype", choices=["float64", "uint8", "bits"], default="float64")
     p.add_argument("--no-csv", action="store_true")
+    p.add_argument("--nearest-strains", action="store_true",
+                   help="sample mode: Hamming distance of every sampled genome to its nearest dataset strain (CSV)")
+    p.add_argument("--pca", action="store_true",
+                   help="sample mode: PCA of the dataset strains with the sampled genomes projected onto it (CSV, PDF)")
     p.add_argument("--genome-path", type=str, default=None,
                    help="GenBank genome (default: <project root>/data/wild_type_sequence.gb)")
     p.add_argument("--output-dir", type=str, default="./minimized_genomes")
@@ -158,9 +166,53 @@ def focused_samples(model, latent_dim, num_samples, noise_level, device):
     return mask, z
 
 
+def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
+    """--nearest-strains / --pca: the sampled genomes against the dataset's strains, on the device."""
+    import numpy as np
+    import pandas as pd
+    from gm2.masks import PackedMasks
+    real = PackedMasks.from_host(merged.iloc[:, :-1].to_numpy(), device=packed.bits.device)
+    mode = args.sampling_mode
+    if args.nearest_strains:
+        ham, idx = packed.nearest(real)
+        path = out_dir / f"{tag}_nearest_strain_{mode}.csv"
+        pd.DataFrame({"sample": np.arange(packed.n), "nearest_strain": merged.index.to_numpy()[idx], "hamming": ham,
+                      "genome_size": sizes}).to_csv(path, index=False)
+        print(f"- Hamming distance to the nearest strain: median {np.median(ham):.0f}, range {ham.min()} - {ham.max()}")
+        print(f"- Samples identical to a dataset strain: {int((ham == 0).sum())}\n- Nearest strains: {path}")
+    if args.pca:
+        from gm2.pca import BinaryPCA
+        pca = BinaryPCA(n_components=2)
+        sc_real = pca.fit_transform(real)
+        sc = np.concatenate([sc_real, pca.transform(packed)])
+        path = out_dir / f"{tag}_pca_real_vs_sampled_{mode}.csv"
+        source = np.array(["real"] * real.n + ["sampled"] * packed.n)
+        pd.DataFrame({"PC1": sc[:, 0], "PC2": sc[:, 1], "source": source,
+                      "phylogroup": list(merged["Phylogroup"].values) + [""] * packed.n}).to_csv(path, index=False)
+        evr = pca.explained_variance_ratio_
+        print(f"- PCA of the {real.n} strains: explained variance ratio PC1 {evr[0]:.4f}, PC2 {evr[1]:.4f}")
+        print(f"- PCA scores (real and sampled): {path}")
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except ImportError:
+            print("- matplotlib is not installed: no PCA scatter plot written")
+            return
+        fig, ax = plt.subplots(figsize=(7, 6))
+        ax.scatter(sc[:real.n, 0], sc[:real.n, 1], s=6, alpha=0.5, label="real strains")
+        ax.scatter(sc[real.n:, 0], sc[real.n:, 1], s=6, alpha=0.5, label="sampled genomes")
+        ax.set_xlabel(f"PC1 ({100 * evr[0]:.1f} %)")
+        ax.set_ylabel(f"PC2 ({100 * evr[1]:.1f} %)")
+        ax.legend()
+        fig.savefig(path.with_suffix(".pdf"))
+        plt.close(fig)
+
+
 def run_sampling(args):
-    """main.py:219-446 without the plots / PCA (out of scope): load the checkpoint, decode in fp32,
-    threshold, count essential genes, save masks (.npy) and the genes x samples CSV."""
+    """main.py:219-446 without the reference's plots: load the checkpoint, decode in fp32, threshold,
+    count essential genes, save masks (.npy) and the genes x samples CSV; --nearest-strains / --pca
+    add the comparison with the dataset's strains (compare_with_strains)."""
     import numpy as np
     import torch
     from gm2.data import load_and_validate_data
@@ -230,6 +282,8 @@ def run_sampling(args):
     print(f"- Genome size range: {np.min(sizes):.0f} - {np.max(sizes):.0f}")
     print(f"- Median essential genes: {np.median(ess):.0f}")
     print(f"- Essential range: {np.min(ess):.0f} - {np.max(ess):.0f}")
+    if args.nearest_strains or args.pca:
+        compare_with_strains(args, packed, sizes, merged, out_dir, config.trainer_version)
     if args.mask_dtype == "bits":
         out = packed.to_host()
     else:

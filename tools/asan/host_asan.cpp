@@ -202,6 +202,22 @@ static void error_paths() {
   CHECK(gm2_resident_layout(-1, 10, GM2_BF16, &ld, &ldb, &rows, &nb, &nbb) != 0, "negative S");
   CHECK(gm2_resident_layout(10, 0, GM2_BF16, &ld, &ldb, &rows, &nb, &nbb) != 0, "zero G");
   CHECK(gm2_reparameterize(-1, &f, &f, &f, &f, nullptr, nullptr, nullptr, nullptr) != 0, "negative n");
+  // bit-row cross products: every refusal is host-side, zero rows return before any launch
+  alignas(16) static uint8_t rows_a[64], rows_b[64];
+  int32_t co[8];
+  int64_t best[4];
+  expect_error(gm2_mask_cooccur(rows_a, -1, 16, rows_b, 2, 16, 100, co, 2, nullptr), "negative", "cooccur na < 0");
+  expect_error(gm2_mask_cooccur(rows_a, 2, 16, rows_b, 2, 16, 0, co, 2, nullptr), "G", "cooccur G = 0");
+  expect_error(gm2_mask_cooccur(rows_a, 2, 24, rows_b, 2, 16, 100, co, 2, nullptr), "pitch", "cooccur lda % 16");
+  expect_error(gm2_mask_cooccur(rows_a, 2, 16, rows_b, 2, 16, 129, co, 2, nullptr), "pitch", "cooccur pitch < G bits");
+  expect_error(gm2_mask_cooccur(rows_a + 8, 2, 16, rows_b, 2, 16, 100, co, 2, nullptr), "aligned", "cooccur misaligned a");
+  expect_error(gm2_mask_cooccur(rows_a, 2, 16, rows_b, 2, 16, 100, co, 1, nullptr), "ldo", "cooccur ldo < nb");
+  CHECK(gm2_mask_cooccur(rows_a, 0, 16, rows_b, 2, 16, 100, co, 2, nullptr) == 0, "cooccur with no a rows");
+  CHECK(gm2_mask_cooccur(rows_a, 2, 16, rows_b, 0, 16, 100, co, 0, nullptr) == 0, "cooccur with no b rows");
+  expect_error(gm2_mask_nearest(rows_a, 2, 16, rows_b, 0, 16, 100, best, nullptr), "nr", "nearest nr = 0");
+  expect_error(gm2_mask_nearest(rows_a, 2, 16, rows_b + 4, 2, 16, 100, best, nullptr), "aligned", "nearest misaligned ref");
+  expect_error(gm2_mask_nearest(rows_a, 2, 16, rows_b, -2, 16, 100, best, nullptr), "negative", "nearest nr < 0");
+  CHECK(gm2_mask_nearest(rows_a, 0, 16, rows_b, 2, 16, 100, best, nullptr) == 0, "nearest with no queries");
   std::string last = gm2_last_error();
   CHECK(!last.empty(), "an error message is kept");
   unsigned flags = 1;
