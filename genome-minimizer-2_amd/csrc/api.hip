@@ -1625,6 +1625,24 @@ int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* r
   });
 }
 
+int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, int64_t G, const int32_t* rows, int64_t n,
+                         int64_t* counts, int accumulate, void* stream) {
+  return guarded([&] {
+    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_gene_counts: G %lld outside [1, 2^31)", (long long)G);
+    if (n < 0) throw Gm2Error("mask_gene_counts: negative n (%lld)", (long long)n);
+    check_bit_rows("mask_gene_counts", "bits", bits, n_rows, ld_bits, G);
+    if (!rows && n > n_rows)
+      throw Gm2Error("mask_gene_counts: n %lld > n_rows %lld without an index list", (long long)n, (long long)n_rows);
+    if (rows && n && n_rows == 0) throw Gm2Error("mask_gene_counts: an index list into n_rows = 0 rows");
+    if ((uintptr_t)rows & 3) throw Gm2Error("mask_gene_counts: rows must be 4-B aligned");
+    if ((uintptr_t)counts & 7) throw Gm2Error("mask_gene_counts: counts must be 8-B aligned");
+    if (!counts) throw Gm2Error("mask_gene_counts: null counts");
+    if (n == 0 && accumulate) return;
+    if (!accumulate) HIP_OK(hipMemsetAsync(counts, 0, (size_t)G * 8, (hipStream_t)stream));
+    launch_gene_counts(bits, n_rows, ld_bits, G, rows, n, counts, (hipStream_t)stream);
+  });
+}
+
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {

@@ -438,6 +438,10 @@ void launch_bit_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t
                         int32_t* out, int64_t ldo, hipStream_t s);
 void launch_bit_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr, int64_t G,
                         int64_t* best, hipStream_t s);
+// per-gene counts: counts[g] += number of the rows rows[0..n) (NULL: rows 0..n-1) of bits with gene g
+// set, g < G (int64, 64-bit atomic adds: the caller zeroes counts to overwrite); n > 0 launches
+void launch_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ldb, int64_t G, const int32_t* rows, int64_t n,
+                        int64_t* counts, hipStream_t s);
 
 // parameter tensor table for the multi-tensor optimizer / shadow kernels
 struct TensorDesc {

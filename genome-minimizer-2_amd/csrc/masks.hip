@@ -7,6 +7,8 @@
 //   * the integer cross products of two sets of rows (no reference kernel: its PCA of the strains,
 //     explore_data/data_exploration.py:394-420, unpacks to float64): popcount(a AND b), the Gram
 //     matrix of 0/1 rows, and the nearest row by popcount(a XOR b). VALU-bound, LDS-tiled.
+//   * genomes per gene (explore_data/data_exploration.py:119-120, `sum(axis=0)` of the 0/1 matrix):
+//     the column sums of the bit rows on bit-sliced carry-save counters, every row byte read once.
 // Mask rows are numpy packbits(bitorder='little') bytes: bit (g & 7) of byte g / 8 = gene g,
 // row pitch ld_bits (multiple of 16 bytes), bits beyond G zero. The first two are HBM-bound integer
 // work: their kernels stream each mask row once with 16-byte (or 4-byte word) loads.
@@ -358,6 +360,159 @@ __global__ __launch_bounds__(256) void k_fill_u64(unsigned long long* __restrict
   if (i < n) p[i] = v;
 }
 
+// ---- per-gene counts: counts[g] += number of the selected rows with gene g set (the column sums of
+// the bit matrix, a positional popcount) ----
+// A workgroup of 4 waves owns a column chunk of 64 x 16 bytes (8,192 genes) and a slab of the selected
+// rows; lane l of every wave owns the 16-byte piece 64 chunk + l of each row (4 words, 128 genes), so
+// one wave-instruction loads 1 KiB of one row. Wave w takes the slab's 8-row blocks w, w + 4, ...:
+// the 8 pieces of a block are loaded together, the next block's before this one is added (two
+// register buffers: 8 KiB in flight per wave under the arithmetic, 128 KiB per CU at 4 workgroups),
+// then added into 8 bit-sliced planes per word (bit b of p[k] = bit k of the running count of gene
+// 32 word + b; 126 VGPRs, no scratch): a carry-save tree reduces the 8 rows into
+// planes 0-2 and one carry word of weight 8 (7 adders of 5 operations), which ripples through planes
+// 3-7 (10 operations): 45 VALU operations per 8 x 32 bits. A block adds at most 8 to a plane counter,
+// so after kGcFlushBlocks = 31 blocks (P = 248 rows of the wave, <= 255) the planes are spilled into
+// the workgroup's LDS counters (ds_add_u32, [gene of the lane][lane] pitched 65: the lanes of one add
+// and of one read below on 64 banks) and cleared. At the end every non-zero LDS sum of a gene < G goes
+// to counts with one 64-bit global atomic add: integer adds commute, so the result is exact whatever
+// order the slabs arrive in.
+constexpr int kGcPieces = 64;         // 16-byte pieces of a row per workgroup (one per lane)
+constexpr int kGcGenes = 128;         // genes of a piece
+constexpr int kGcBlock = 8;           // rows per carry-save block
+constexpr int kGcWaves = 4;
+constexpr int kGcFlushBlocks = 31;    // blocks between two spills: 31 * 8 = 248 <= 2^8 - 1
+constexpr int kGcSlabRows = 1024;     // fewest rows of a slab (a multiple of kGcWaves * kGcBlock)
+constexpr int kGcTargetWgs = 1024;    // workgroups of a large call: 256 CUs x 4 resident (33 KB of LDS
+                                      // each); 2,048 measured 3 % slower
+constexpr int kGcPitch = kGcPieces + 1;
+
+// (h, l) = carry and sum of a + b + c, bit-sliced
+#define GM2_CSA(h, l, a, b, c)               \
+  do {                                       \
+    const uint32_t u_ = (a) ^ (b), c_ = (c); \
+    (h) = ((a) & (b)) | (u_ & c_);           \
+    (l) = u_ ^ c_;                           \
+  } while (0)
+
+// the 8 pieces of the block at list position i (rows beyond r1 and lanes beyond the row: zero; their
+// loads go to the last row / piece instead of branching)
+template <bool kIdx>
+__device__ __forceinline__ void gc_load(uint4 (&x)[kGcBlock], const uint4* __restrict__ col, int64_t ld16,
+                                        const int32_t* __restrict__ rows, int64_t n_rows, int64_t i, int64_t r1,
+                                        bool active) {
+#pragma unroll
+  for (int u = 0; u < kGcBlock; ++u) {
+    int64_t src = min(i + u, r1 - 1);
+    if (kIdx) {
+      src = rows[src];
+      GM2_DBG(src >= 0 && src < n_rows, kDbgGeneRows);
+    }
+    x[u] = col[src * ld16];
+  }
+#pragma unroll
+  for (int u = 0; u < kGcBlock; ++u)
+    if (!(active && i + u < r1)) x[u] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// 8 rows of one word column into its planes
+__device__ __forceinline__ void gc_add(uint32_t (&p)[8], uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
+                                       uint32_t x4, uint32_t x5, uint32_t x6, uint32_t x7) {
+  uint32_t t2a, t2b, t4a, t4b, c8;
+  GM2_CSA(t2a, p[0], p[0], x0, x1);
+  GM2_CSA(t2b, p[0], p[0], x2, x3);
+  GM2_CSA(t4a, p[1], p[1], t2a, t2b);
+  GM2_CSA(t2a, p[0], p[0], x4, x5);
+  GM2_CSA(t2b, p[0], p[0], x6, x7);
+  GM2_CSA(t4b, p[1], p[1], t2a, t2b);
+  GM2_CSA(c8, p[2], p[2], t4a, t4b);
+#pragma unroll
+  for (int k = 3; k < 8; ++k) {
+    const uint32_t c = p[k] & c8;
+    p[k] ^= c8;
+    c8 = c;
+  }
+}
+
+struct GcPlanes {
+  uint32_t x[8], y[8], z[8], w[8];  // the planes of the lane's 4 words
+};
+
+// the planes' counts into the LDS counters of the lane's 128 genes; planes cleared
+__device__ __forceinline__ void gc_flush_word(uint32_t (&p)[8], unsigned* __restrict__ l) {
+#pragma unroll
+  for (int b = 0; b < 32; ++b) {
+    uint32_t v = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v += ((p[k] >> b) & 1u) << k;
+    atomicAdd(&l[b * kGcPitch], v);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) p[k] = 0u;
+}
+__device__ __forceinline__ void gc_flush(GcPlanes& pl, unsigned* __restrict__ lsum, int lane) {
+  gc_flush_word(pl.x, lsum + lane);
+  gc_flush_word(pl.y, lsum + 32 * kGcPitch + lane);
+  gc_flush_word(pl.z, lsum + 64 * kGcPitch + lane);
+  gc_flush_word(pl.w, lsum + 96 * kGcPitch + lane);
+}
+
+template <bool kIdx>
+__global__ __launch_bounds__(256) void k_gene_counts(const uint8_t* __restrict__ bits, int64_t n_rows, int64_t ldb, int n16,
+                                                   int64_t G, const int32_t* __restrict__ rows, int64_t n,
+                                                   int64_t slab_rows, int nc, unsigned long long* __restrict__ counts) {
+  __shared__ __attribute__((aligned(16))) unsigned lsum[kGcGenes * kGcPitch];
+  const int chunk = blockIdx.x % nc;  // chunks fastest: neighbouring workgroups read the same rows
+  const int64_t slab = blockIdx.x / nc;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int piece = chunk * kGcPieces + lane;
+  const bool active = piece < n16;  // (pieces beyond roundup(G, 128) / 128 are never read)
+  const uint4* col = (const uint4*)bits + min(piece, n16 - 1);
+  const int64_t ld16 = ldb / 16;
+  const int64_t r1 = min(n, (slab + 1) * slab_rows);
+  for (int i = threadIdx.x; i < kGcGenes * kGcPitch / 4; i += 256) ((uint4*)lsum)[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
+
+  GcPlanes pl;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) pl.x[k] = pl.y[k] = pl.z[k] = pl.w[k] = 0u;
+  int blocks = 0;
+  auto add = [&](const uint4(&x)[kGcBlock]) __attribute__((always_inline)) {
+    gc_add(pl.x, x[0].x, x[1].x, x[2].x, x[3].x, x[4].x, x[5].x, x[6].x, x[7].x);
+    gc_add(pl.y, x[0].y, x[1].y, x[2].y, x[3].y, x[4].y, x[5].y, x[6].y, x[7].y);
+    gc_add(pl.z, x[0].z, x[1].z, x[2].z, x[3].z, x[4].z, x[5].z, x[6].z, x[7].z);
+    gc_add(pl.w, x[0].w, x[1].w, x[2].w, x[3].w, x[4].w, x[5].w, x[6].w, x[7].w);
+    if (++blocks == kGcFlushBlocks) {
+      gc_flush(pl, lsum, lane);
+      blocks = 0;
+    }
+  };
+
+  constexpr int kStep = kGcWaves * kGcBlock;
+  int64_t i = slab * slab_rows + (int64_t)wave * kGcBlock;
+  if (i < r1) {
+    uint4 xa[kGcBlock], xb[kGcBlock];
+    gc_load<kIdx>(xa, col, ld16, rows, n_rows, i, r1, active);
+    while (true) {  // (a load beyond the slab reads its last row again and keeps zeros)
+      gc_load<kIdx>(xb, col, ld16, rows, n_rows, i + kStep, r1, active);
+      add(xa);
+      if ((i += kStep) >= r1) break;
+      gc_load<kIdx>(xa, col, ld16, rows, n_rows, i + kStep, r1, active);
+      add(xb);
+      if ((i += kStep) >= r1) break;
+    }
+    gc_flush(pl, lsum, lane);
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int k = 0; k < kGcGenes * kGcPieces / 256; ++k) {
+    const int gl = threadIdx.x + 256 * k;  // gene 128 (gl >> 7) + (gl & 127) of the chunk
+    const unsigned v = lsum[(gl & (kGcGenes - 1)) * kGcPitch + (gl >> 7)];
+    const int64_t g = (int64_t)chunk * (kGcGenes * kGcPieces) + gl;
+    if (g < G && v) atomicAdd(&counts[g], (unsigned long long)v);
+  }
+}
+#undef GM2_CSA
+
 // 1-D grid of ta x tb tiles
 unsigned bit_grid(int64_t ra, int64_t rb, int* tiles_b) {
   const int64_t ta = (ra + kBgTile - 1) / kBgTile, tb = (rb + kBgTile - 1) / kBgTile;
@@ -390,6 +545,28 @@ void launch_bit_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t
   const int64_t kb = (G + 127) / 128 * 16;
   hipLaunchKernelGGL(k_bit_nearest, dim3(grid), dim3(256), 0, s, q, nq, ldq, ref, nr, ldr, kb,
                      (unsigned long long*)best, tr);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ldb, int64_t G, const int32_t* rows, int64_t n,
+                        int64_t* counts, hipStream_t s) {
+  if (n <= 0) return;
+  // nc column chunks x enough row slabs for kGcTargetWgs workgroups, a slab no shorter than
+  // kGcSlabRows: at most 8,192 atomics (64 KB) per workgroup against >= 1 MB of rows read
+  const int64_t nw = (G + 127) / 128, nc = (nw + kGcPieces - 1) / kGcPieces;
+  const int64_t slabs = std::max<int64_t>(1, std::min<int64_t>(kGcTargetWgs / nc, (n + kGcSlabRows - 1) / kGcSlabRows));
+  const int64_t step = kGcWaves * kGcBlock;
+  const int64_t slab_rows = ((n + slabs - 1) / slabs + step - 1) / step * step;
+  const int64_t used = (n + slab_rows - 1) / slab_rows;
+  if (slab_rows > 0x7fffffff || used * nc > 0x7fffffff)
+    throw Gm2Error("mask_gene_counts: %lld rows x %lld genes are more than one launch holds", (long long)n, (long long)G);
+  const dim3 grid((unsigned)(used * nc));
+  if (rows)
+    hipLaunchKernelGGL(k_gene_counts<true>, grid, dim3(256), 0, s, bits, n_rows, ldb, (int)nw, G, rows, n, slab_rows,
+                       (int)nc, (unsigned long long*)counts);
+  else
+    hipLaunchKernelGGL(k_gene_counts<false>, grid, dim3(256), 0, s, bits, n_rows, ldb, (int)nw, G, rows, n, slab_rows,
+                       (int)nc, (unsigned long long*)counts);
   GM2_CHECK_LAUNCH();
 }
 

@@ -7,6 +7,10 @@ consumers run on it without leaving the device:
   * count_essential_genes (utils/extras.py:49-87)        -> PackedMasks.count_groups
   * genome sizes (main.py:376-380 statistics)             -> PackedMasks.row_sizes
   * masks_to_gene_lists (explore_data/binary_converter.py:19-76) -> PackedMasks.gene_index_csr
+  * genomes per gene, `data_without_lineage.sum(axis=1)` (explore_data/data_exploration.py:119-120),
+    and the genes-in-at-least-t-genomes curve built on it (:213-230)
+                                                          -> PackedMasks.gene_counts / gene_counts_by
+                                                             (tables and summaries: gm2/genefreq.py)
 and `to_host` returns the packed rows (8x less PCIe than u8) for the .npy writers.
 """
 from __future__ import annotations
@@ -102,6 +106,61 @@ class PackedMasks:
         native.mask_nearest(self.bits, self.n, self.ld, other.bits, other.n, other.ld, self.G, best)
         key = best.cpu().numpy()
         return key >> 32, key & 0xFFFFFFFF
+
+    def _row_list(self, rows):
+        """An index array or a boolean mask of length n -> device int32 indices. Host arrays are
+        range-checked here; a device tensor's entries are the caller's (the debug build checks them)."""
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype == torch.bool:
+                if rows.numel() != self.n:
+                    raise ValueError(f"gene_counts: a boolean mask of {rows.numel()} rows for {self.n}")
+                rows = torch.nonzero(rows.reshape(-1)).reshape(-1)
+            return rows.reshape(-1).to(device=self.bits.device, dtype=torch.int32).contiguous()
+        r = np.asarray(rows)
+        if r.dtype == bool:
+            if r.shape != (self.n,):
+                raise ValueError(f"gene_counts: a boolean mask of shape {r.shape} for {self.n} rows")
+            r = np.flatnonzero(r)
+        elif r.size == 0:
+            r = np.zeros(0, dtype=np.int64)
+        elif r.ndim != 1 or not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("gene_counts: rows must be a 1-D integer index array or a boolean mask")
+        if r.size and (r.min() < 0 or r.max() >= self.n):
+            raise ValueError(f"gene_counts: row indices outside [0, {self.n})")
+        return torch.from_numpy(r.astype(np.int32)).to(self.bits.device)
+
+    def gene_counts(self, rows=None, out=None):
+        """Genomes per gene (binary.sum(axis=0); explore_data/data_exploration.py:119-120) -> device
+        int64 [G]. rows: an integer index array (repeats counted each time) or a boolean mask of
+        length n, None = every row. out (device int64 [G]) is added to and returned."""
+        if out is None:
+            counts, acc = torch.empty(self.G, dtype=torch.int64, device=self.bits.device), False
+        else:
+            if out.dtype != torch.int64 or out.numel() != self.G or not out.is_contiguous() or \
+                    out.device != self.bits.device:
+                raise ValueError(f"gene_counts: out must be a contiguous device int64 [{self.G}] tensor")
+            counts, acc = out, True
+        if rows is None:
+            native.mask_gene_counts(self.bits, self.n, self.ld, self.G, None, self.n, counts, acc)
+        else:
+            idx = self._row_list(rows)
+            native.mask_gene_counts(self.bits, self.n, self.ld, self.G, idx if idx.numel() else None, idx.numel(),
+                                    counts, acc)
+        return counts
+
+    def gene_counts_by(self, labels):
+        """Per-class gene counts: (classes (np.unique order), int64 numpy [K, G]), one call per class
+        with that class's index list, so the matrix is read once in total; the rows of the table
+        sum to gene_counts()."""
+        lab = np.asarray(labels)
+        if lab.shape != (self.n,):
+            raise ValueError(f"gene_counts_by: {lab.shape} labels for {self.n} rows")
+        classes, inv = np.unique(lab, return_inverse=True)
+        table = torch.empty(len(classes), self.G, dtype=torch.int64, device=self.bits.device)
+        for k in range(len(classes)):
+            idx = torch.from_numpy(np.flatnonzero(inv == k).astype(np.int32)).to(self.bits.device)
+            native.mask_gene_counts(self.bits, self.n, self.ld, self.G, idx, idx.numel(), table[k])
+        return classes, table.cpu().numpy()
 
     def to_host(self):
         """numpy packbits rows [n, ceil(G/8)] (bitorder 'little')."""

@@ -249,6 +249,21 @@ int gm2_mask_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b
 int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr,
                      int64_t G, int64_t* best, void* stream);
 
+/* (ABI 6, additive) counts[g] (+)= number of the selected rows with gene g set, g < G: the column
+ * sums of the 0/1 matrix (explore_data/data_exploration.py:119-120 on the real strains).
+ * bits [n_rows][ld_bits]: the packed layout above (pitch a multiple of 16 covering G, rows 16-B
+ * aligned, bits beyond G zero). rows = NULL: rows 0..n-1 (n <= n_rows); else n int32 row indices in
+ * [0, n_rows), a repeated index counted each time. accumulate = 0: counts is overwritten; != 0:
+ * added to (chunked sampling sums into one vector). counts: int64 [G], 8-B aligned; nothing at or
+ * beyond counts[G] is written, bytes of a row beyond roundup(G,128)/8 are never read.
+ * Stream-ordered, no allocation: every row byte is read once, workgroup partials are added to counts
+ * with 64-bit integer atomics (exact, independent of the run order).
+ * Return < 0 (see the last-error message) on a negative n or n_rows, n > n_rows without an index
+ * list, G < 1, a bad pitch or alignment, counts == NULL. n == 0: counts is zeroed (accumulate = 0) or
+ * left alone without touching the device (accumulate != 0). */
+int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, int64_t G, const int32_t* rows,
+                         int64_t n, int64_t* counts, int accumulate, void* stream);
+
 /* calculate_reconstruction_metrics (training/evaluation/metrics.py:19-64) without materialising the
  * reconstruction: eval-mode model(x) of `batch` (eps given: the reference samples z there too), then
  * per strain counts[i] = (TP, FP, FN) of (recon > threshold) against the strain's genes. */

@@ -34,7 +34,10 @@ and essential-gene counts are computed there (gm2/masks.py) and only the packed 
 --nearest-strains / --pca (sample mode, both off by default) compare the sampled genomes with the
 dataset's strains on the packed rows (gm2_mask_nearest / gm2_mask_cooccur, gm2/pca.py): the nearest
 strain of every sample by Hamming distance, and the PCA of the strains (the reference's Figure 2a)
-with the samples projected onto its axes.
+with the samples projected onto its axes. --gene-frequencies (sample mode, off by default) counts the
+genomes per gene of the sampled set and of the strains on the packed rows (gm2_mask_gene_counts,
+gm2/genefreq.py) and writes the real-vs-sampled frequency table, per phylogroup for the strains and,
+with --nearest-strains, for the samples by their nearest strain's phylogroup.
 """
 import argparse
 import os
@@ -73,6 +76,8 @@ def parse_arguments(argv=None):
                    help="sample mode: Hamming distance of every sampled genome to its nearest dataset strain (CSV)")
     p.add_argument("--pca", action="store_true",
                    help="sample mode: PCA of the dataset strains with the sampled genomes projected onto it (CSV, PDF)")
+    p.add_argument("--gene-frequencies", action="store_true",
+                   help="sample mode: per-gene frequency of the sampled genomes against the dataset strains (CSV)")
     p.add_argument("--genome-path", type=str, default=None,
                    help="GenBank genome (default: <project root>/data/wild_type_sequence.gb)")
     p.add_argument("--output-dir", type=str, default="./minimized_genomes")
@@ -166,13 +171,41 @@ def focused_samples(model, latent_dim, num_samples, noise_level, device):
     return mask, z
 
 
+def gene_frequencies(packed, real, merged, nearest_idx, path):
+    """--gene-frequencies: genomes per gene of the sampled set and of the strains, both counted on the
+    packed rows (PackedMasks.gene_counts; no mask crosses PCIe for it), the strains also per phylogroup,
+    the samples too when every sample has a nearest strain (--nearest-strains) whose phylogroup labels it."""
+    import numpy as np
+    from gm2 import genefreq
+    groups = merged.iloc[:, -1].to_numpy()
+    classes, by = real.gene_counts_by(groups)
+    real_by = (classes, by, [int((groups == c).sum()) for c in classes])
+    sampled_by = None
+    if nearest_idx is not None:
+        labels = groups[nearest_idx]
+        s_classes, s_by = packed.gene_counts_by(labels)
+        sampled_by = (s_classes, s_by, [int((labels == c).sum()) for c in s_classes])
+    table = genefreq.frequency_table(merged.columns[:-1].to_numpy(), genefreq.gene_counts(real), real.n,
+                                     genefreq.gene_counts(packed), packed.n, real_by, sampled_by)
+    table.to_csv(path, index=False)
+    s = genefreq.frequency_summary(table)
+    print(f"- Gene frequencies, sampled vs real: Pearson r {s['pearson_r']:.4f}, |delta| mean {s['mean_abs_delta']:.4f}, "
+          f"max {s['max_abs_delta']:.4f}")
+    print(f"- Core genes of the strains (>= 99 %): {s['real_core']}; still core in the samples: "
+          f"{s['real_core_sampled_core']}, at least soft core (>= 95 %): {s['real_core_sampled_soft_core']}")
+    print(f"- Genes of the strains never sampled: {s['real_never_sampled']}; sampled but in no strain: "
+          f"{s['sampled_absent_from_real']}\n- Gene frequencies: {path}")
+
+
 def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
-    """--nearest-strains / --pca: the sampled genomes against the dataset's strains, on the device."""
+    """--nearest-strains / --pca / --gene-frequencies: the sampled genomes against the dataset's strains,
+    on the device."""
     import numpy as np
     import pandas as pd
     from gm2.masks import PackedMasks
     real = PackedMasks.from_host(merged.iloc[:, :-1].to_numpy(), device=packed.bits.device)
     mode = args.sampling_mode
+    idx = None
     if args.nearest_strains:
         ham, idx = packed.nearest(real)
         path = out_dir / f"{tag}_nearest_strain_{mode}.csv"
@@ -180,6 +213,8 @@ def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
                       "genome_size": sizes}).to_csv(path, index=False)
         print(f"- Hamming distance to the nearest strain: median {np.median(ham):.0f}, range {ham.min()} - {ham.max()}")
         print(f"- Samples identical to a dataset strain: {int((ham == 0).sum())}\n- Nearest strains: {path}")
+    if args.gene_frequencies:
+        gene_frequencies(packed, real, merged, idx, out_dir / f"{tag}_gene_frequencies_{mode}.csv")
     if args.pca:
         from gm2.pca import BinaryPCA
         pca = BinaryPCA(n_components=2)
@@ -282,7 +317,7 @@ def run_sampling(args):
     print(f"- Genome size range: {np.min(sizes):.0f} - {np.max(sizes):.0f}")
     print(f"- Median essential genes: {np.median(ess):.0f}")
     print(f"- Essential range: {np.min(ess):.0f} - {np.max(ess):.0f}")
-    if args.nearest_strains or args.pca:
+    if args.nearest_strains or args.pca or args.gene_frequencies:
         compare_with_strains(args, packed, sizes, merged, out_dir, config.trainer_version)
     if args.mask_dtype == "bits":
         out = packed.to_host()

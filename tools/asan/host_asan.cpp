@@ -218,6 +218,21 @@ static void error_paths() {
   expect_error(gm2_mask_nearest(rows_a, 2, 16, rows_b + 4, 2, 16, 100, best, nullptr), "aligned", "nearest misaligned ref");
   expect_error(gm2_mask_nearest(rows_a, 2, 16, rows_b, -2, 16, 100, best, nullptr), "negative", "nearest nr < 0");
   CHECK(gm2_mask_nearest(rows_a, 0, 16, rows_b, 2, 16, 100, best, nullptr) == 0, "nearest with no queries");
+  // per-gene counts: the same vocabulary; no rows to add into a kept vector returns before any device call
+  int64_t gc[128];
+  int32_t idx[2] = {0, 1};
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 100, nullptr, -1, gc, 0, nullptr), "negative", "gene_counts n < 0");
+  expect_error(gm2_mask_gene_counts(rows_a, -2, 16, 100, nullptr, 0, gc, 0, nullptr), "negative", "gene_counts n_rows < 0");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 100, nullptr, 3, gc, 0, nullptr), "n_rows", "gene_counts n > n_rows");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 0, nullptr, 2, gc, 0, nullptr), "G", "gene_counts G = 0");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 24, 100, nullptr, 2, gc, 0, nullptr), "pitch", "gene_counts pitch % 16");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 129, nullptr, 2, gc, 0, nullptr), "pitch", "gene_counts pitch < G bits");
+  expect_error(gm2_mask_gene_counts(rows_a + 8, 2, 16, 100, nullptr, 2, gc, 0, nullptr), "aligned", "gene_counts misaligned bits");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 100, idx, 2, (int64_t*)((char*)gc + 4), 1, nullptr), "aligned",
+               "gene_counts misaligned counts");
+  expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 100, idx, 2, nullptr, 1, nullptr), "null", "gene_counts null counts");
+  CHECK(gm2_mask_gene_counts(rows_a, 2, 16, 100, nullptr, 0, gc, 1, nullptr) == 0, "gene_counts of no rows, accumulating");
+  CHECK(gm2_mask_gene_counts(rows_a, 2, 16, 100, idx, 0, gc, 1, nullptr) == 0, "gene_counts of an empty list, accumulating");
   std::string last = gm2_last_error();
   CHECK(!last.empty(), "an error message is kept");
   unsigned flags = 1;
