@@ -508,6 +508,95 @@ def manual_grads_emulated(P, S, x, eps, beta, wgamma, operand_round=None, dtype=
     return {n: G[n] for n in P}, sums
 
 
+def manual_forward_backward_emulated(P, S, x, eps, dprobs, dmu, dlv, train, operand_round=None,
+                                     dtype=torch.float64):
+    """VAE.forward (model.py:95-113) and the backward of its outputs (probs, mu, logvar) for given
+    upstream gradients dprobs [n, G], dmu and dlv [n, L] (None = zero), with explicit formulas (no
+    autograd) in `dtype`: what gm2_forward + gm2_backward_outputs compute. No loss terms (beta = 0).
+    train: batch-statistics BatchNorm (manual_grads_emulated's chain); else running-statistics
+    BatchNorm, an affine map per feature: dy = gamma * invstd_running * do, and the pre-BatchNorm
+    Linear biases have a real gradient dy.sum(0). `operand_round` is applied at the points
+    manual_grads_emulated documents (weights, post-ReLU activations, z, dl = dprobs * (1 - p) * p,
+    every dY, the head gradient). Returns ({probs, mu, logvar, and the output layer's logit},
+    {name: gradient})."""
+    r = operand_round if operand_round is not None else (lambda t: t)
+    dt = dtype
+    Pd = {k: v.to(dt) for k, v in P.items()}
+    Wr = {k: r(v).to(dt) if v.dim() == 2 else v.to(dt) for k, v in P.items()}
+    x = x.to(dt)
+    eps = eps.to(dt)
+    B = x.shape[0]
+    cache = []
+
+    def blk(lin, bn, a_rounded):
+        y = a_rounded @ Wr[lin + ".weight"].t() + Pd[lin + ".bias"]
+        if train:
+            mean = y.mean(0)
+            var = ((y - mean) ** 2).mean(0)
+        else:
+            mean = S[bn + ".running_mean"].to(dt)
+            var = S[bn + ".running_var"].to(dt)
+        invstd = 1.0 / torch.sqrt(var + BN_EPS)
+        xhat = (y - mean) * invstd
+        o = xhat * Pd[bn + ".weight"] + Pd[bn + ".bias"]
+        a = torch.relu(o)
+        cache.append((lin, bn, a_rounded, xhat, invstd, o))
+        return r(a).to(dt)
+    h = x
+    for i in range(3):
+        h = blk(f"encoder.{3*i}", f"encoder.{3*i+1}", h)
+    h2 = h
+    mu = h2 @ Wr["mean_layer.weight"].t() + Pd["mean_layer.bias"]
+    lv = h2 @ Wr["logvar_layer.weight"].t() + Pd["logvar_layer.bias"]
+    std = torch.exp(0.5 * lv)
+    z = mu + std * eps
+    h = r(z).to(dt)
+    for i in range(3):
+        h = blk(f"decoder.{3*i}", f"decoder.{3*i+1}", h)
+    a5 = h
+    logit = a5 @ Wr["decoder.9.weight"].t() + Pd["decoder.9.bias"]
+    p = torch.sigmoid(logit)
+    out = {"probs": p, "mu": mu, "logvar": lv, "logit": logit}
+    G = {}
+    dl = r(dprobs.to(dt) * (1 - p) * p).to(dt)
+    G["decoder.9.weight"] = dl.t() @ a5
+    G["decoder.9.bias"] = dl.sum(0)
+    da = dl @ Wr["decoder.9.weight"]
+    del dl
+
+    def blk_bwd(entry, da):
+        lin, bn, a, xhat, invstd, o = entry
+        do = da * (o > 0).to(dt)
+        sdo = do.sum(0)
+        sdx = (do * xhat).sum(0)
+        G[bn + ".weight"] = sdx
+        G[bn + ".bias"] = sdo
+        if train:
+            dy = Pd[bn + ".weight"] * invstd / B * (B * do - sdo - xhat * sdx)
+        else:
+            dy = Pd[bn + ".weight"] * invstd * do
+        G[lin + ".bias"] = dy.sum(0)
+        dyr = r(dy).to(dt)
+        G[lin + ".weight"] = dyr.t() @ a
+        return dyr @ Wr[lin + ".weight"]
+    for e in reversed(cache[3:]):
+        da = blk_bwd(e, da)
+    dz = da
+    dmu_t = dz if dmu is None else dz + dmu.to(dt)
+    dlv_t = dz * eps * std * 0.5
+    if dlv is not None:
+        dlv_t = dlv_t + dlv.to(dt)
+    G["mean_layer.bias"] = dmu_t.sum(0)
+    G["logvar_layer.bias"] = dlv_t.sum(0)
+    dmur, dlvr = r(dmu_t).to(dt), r(dlv_t).to(dt)
+    G["mean_layer.weight"] = dmur.t() @ h2
+    G["logvar_layer.weight"] = dlvr.t() @ h2
+    da = dmur @ Wr["mean_layer.weight"] + dlvr @ Wr["logvar_layer.weight"]
+    for e in reversed(cache[:3]):
+        da = blk_bwd(e, da)
+    return out, {n: G[n] for n in P}
+
+
 def bf16_round(t):
     """Round to bf16 (RNE) and back: what libgm2's bf16 path stores for a GEMM operand."""
     return t.to(torch.bfloat16).to(t.dtype)

@@ -61,13 +61,37 @@ def test_count_essential_on_device_matches_reference(name):
     np.testing.assert_array_equal(count_essential_genes(pm, d), g[f"{name}_counts"])
 
 
-@pytest.mark.parametrize("G,N,ngroups", [(55039, 1000, 300), (1000, 130, 900), (4100, 70, 0)])
-def test_count_groups_whole_row_kernel(G, N, ngroups):
+def _count_groups_variant(ldb, ngroups):
+    """Which of launch_count_groups' three kernels a call takes (masks.hip), from the row pitch and
+    the group count: the whole-row kernel needs 16-B row pieces and mask + list (ldb + 4 (ngroups + 1)
+    bytes) within 64 KB of LDS, and stages the waves' rows in LDS when 4 more rows still fit."""
+    lds = ldb + 4 * (ngroups + 1)
+    if ldb % 16 or lds > 65536:
+        return "per_wave"
+    return "staged" if (lds + 15) // 16 * 16 + 4 * ldb <= 65536 else "unstaged"
+
+
+@pytest.mark.parametrize("G,N,ngroups,pitch,variant", [
+    pytest.param(55039, 1000, 300, None, "staged", id="55039-1000-300"),
+    pytest.param(1000, 130, 900, None, "staged", id="1000-130-900"),
+    pytest.param(4100, 70, 0, None, "staged", id="4100-70-0"),
+    # ldb = 512: 512 + 4 * 16001 <= 65536 < 5 * 512 + 4 * 16001: whole-row, rows not staged
+    pytest.param(4096, 70, 16000, None, "unstaged", id="4096-70-16000-unstaged"),
+    # 512 + 4 * 16401 > 65536: the per-wave kernel
+    pytest.param(4096, 70, 16400, None, "per_wave", id="4096-70-16400-per_wave"),
+    # pitch 136 (136 % 16 = 8): the per-wave kernel; PackedMasks refuses that pitch
+    pytest.param(1000, 70, 300, 136, "per_wave", id="1000-70-300-pitch136")])
+def test_count_groups_whole_row_kernel(G, N, ngroups, pitch, variant):
     """gm2_mask_count_groups (whole-row form: single-position groups through an LDS bit mask, the
     rest listed) == a numpy count of the reference's rule (a group counts when any of its positions
     is set) with single-position groups on distinct and on shared genes, multi-position groups,
     empty groups and positions at the row's last bits; G = 1000 with 900 groups puts most groups on
-    genes another group already holds."""
+    genes another group already holds. The last three cases take the launcher's other two kernels
+    (whole-row without LDS row staging, and the per-wave kernel); which one a case takes is asserted
+    from the launcher's LDS arithmetic, so a change of its thresholds fails here."""
+    ldb = pitch or native.packed_row_bytes(G)
+    assert native.packed_row_bytes(G) == (G + 127) // 128 * 16 and ldb * 8 >= G
+    assert _count_groups_variant(ldb, ngroups) == variant
     rng = np.random.Generator(np.random.PCG64(G + ngroups))
     M = rng.random((N, G)) < 0.3
     M[0] = True
@@ -86,9 +110,14 @@ def test_count_groups_whole_row_kernel(G, N, ngroups):
     for x in groups:
         if x:
             want += M[:, x].any(axis=1)
-    pm = PackedMasks.from_host(M, threshold=True)
+    bits = PackedMasks.from_host(M, threshold=True).bits
+    if pitch:
+        wide = torch.zeros(N, pitch, dtype=torch.uint8, device="cuda")
+        wide[:, :bits.shape[1]] = bits
+        bits = wide
+    assert bits.shape[1] == ldb and bits.is_contiguous() and bits.data_ptr() % 16 == 0
     counts = torch.zeros(N, dtype=torch.int32, device="cuda")
-    native.mask_count_groups(pm.bits, N, pm.bits.shape[1], torch.from_numpy(offs).cuda(), ngroups,
+    native.mask_count_groups(bits, N, ldb, torch.from_numpy(offs).cuda(), ngroups,
                              torch.from_numpy(pos).cuda(), counts)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(counts.cpu().numpy(), want)
