@@ -1643,6 +1643,26 @@ int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, i
   });
 }
 
+int gm2_mask_transpose(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, uint8_t* out, int64_t ld_out,
+                       void* stream) {
+  return guarded([&] {
+    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_transpose: G %lld outside [1, 2^31)", (long long)G);
+    if (n > 0x7fffffff) throw Gm2Error("mask_transpose: n %lld outside [0, 2^31)", (long long)n);
+    check_bit_rows("mask_transpose", "bits", bits, n, ld_bits, G);
+    if (ld_out <= 0 || (ld_out & 15) || ld_out < (n + 7) / 8)
+      throw Gm2Error("mask_transpose: pitch of out (%lld) must be a multiple of 16 bytes covering n = %lld bits",
+                     (long long)ld_out, (long long)n);
+    if ((uintptr_t)out & 15) throw Gm2Error("mask_transpose: rows of out must be 16-B aligned");
+    if (n == 0) return;
+    if (!out) throw Gm2Error("mask_transpose: null out");
+    // the bytes read: rows of roundup(G, 128) / 8; the bytes written: G rows of roundup(n, 128) / 8
+    const uintptr_t b0 = (uintptr_t)bits, b1 = b0 + (uintptr_t)((n - 1) * ld_bits + gm2_packed_row_bytes(G));
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)((G - 1) * ld_out + gm2_packed_row_bytes(n));
+    if (b0 < o1 && o0 < b1) throw Gm2Error("mask_transpose: out and bits overlap");
+    launch_bit_transpose(bits, n, ld_bits, G, out, ld_out, (hipStream_t)stream);
+  });
+}
+
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {

@@ -71,6 +71,7 @@ enum DebugBit : unsigned {
   kDbgBandBlock = 128u,    // band-list overflow: a flagged 256 x 256 block outside the block grid
   kDbgBitRows = 256u,      // k_bit_cooccur / k_bit_nearest: a store outside out / a winner outside [0, nr)
   kDbgGeneRows = 512u,     // k_gene_counts: an index-list entry outside [0, n_rows)
+  kDbgTranspose = 1024u,   // k_bit_transpose: a store outside the G rows x packed_row_bytes(n) written extent
 };
 #ifdef GM2_DEBUG
 namespace {

@@ -442,6 +442,11 @@ void launch_bit_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t
 // set, g < G (int64, 64-bit atomic adds: the caller zeroes counts to overwrite); n > 0 launches
 void launch_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ldb, int64_t G, const int32_t* rows, int64_t n,
                         int64_t* counts, hipStream_t s);
+// bit transpose: out [G][ldo] row g, bit i = bits [n][ldb] row i, bit g; bytes [0, roundup(n, 128) / 8)
+// of every out row are written (bits >= n zero), the first roundup(G, 128) / 8 bytes of a bits row
+// read; out and bits 16-B aligned, pitches multiples of 16, no overlap; n > 0 launches
+void launch_bit_transpose(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G, uint8_t* out, int64_t ldo,
+                          hipStream_t s);
 
 // parameter tensor table for the multi-tensor optimizer / shadow kernels
 struct TensorDesc {

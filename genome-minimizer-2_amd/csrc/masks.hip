@@ -513,6 +513,113 @@ __global__ __launch_bounds__(256) void k_gene_counts(const uint8_t* __restrict__
 }
 #undef GM2_CSA
 
+// ---- bit transpose: out row g, bit i = bits row i, bit g (the same packed layout on both sides) ----
+// A workgroup of 512 lanes owns a tile of 1,024 source rows x 512 genes: 64 bytes of each source row in,
+// one whole 128-byte line of each of 512 output rows out (the other way round, 512 rows x 1,024 genes
+// with whole lines in and half lines out, measured 1.3x slower). Lane (rb = t / 16, j = t % 16) owns the
+// 32 x 32 bit block of rows 32 rb .. 32 rb + 31 and gene word j: its 32 global loads (one word each;
+// the 16 lanes of one rb read 64 contiguous bytes of a row, a wave 4 rows per load) are all in
+// flight together. In a tile that reaches past the n rows or past roundup(G, 128) / 32 words the loads
+// go to the last valid row / word instead and are zeroed in registers, so no lane branches; an interior
+// tile (a test uniform over the workgroup) skips the clamps. The block is transposed in registers by
+// the 5 block-swap stages of the recursive 32 x 32 transpose (16 swaps of 6 operations each per
+// stage: 480 VALU operations per 1,024 bits and lane, no cross-lane traffic), after which register b
+// holds the 4 output bytes (rows 32 rb ..) of gene 32 j + b.
+// These go through an LDS tile [512 genes][32 words] (64 KB, two workgroups per CU) so that the
+// global stores are whole lines: the word of (gene g, row block rb) sits at column
+// (rb + 2 (g / 32) + g % 4) % 32 of row g. The pitch is a whole 128-byte bank row (ds_write_b32 and
+// ds_read_b32 bank = word address mod 32 = the column, conflicts counted per 32-lane half):
+//   * a store's half holds 2 row blocks (rb even, rb + 1) x 16 words j of one register b: columns
+//     rb' + 2 j + const, 32 different banks;
+//   * a read's half holds the 8 pieces q of 4 neighbouring genes (g % 4 = 0..3, one g / 32) and reads
+//     word c of each piece: columns 4 q + g % 4 + const, 32 different banks.
+// Each lane then gathers 8 16-byte pieces (4 ds_read_b32 each) and stores them with 16-byte stores:
+// 8 neighbouring lanes write one 128-byte line of one gene row.
+constexpr int kTrThreads = 512;           // one 32 x 32 block per lane
+constexpr int kTrWords = 16;              // 32-gene words of a tile (64 bytes of a source row)
+constexpr int kTrRb = kTrThreads / kTrWords;  // row blocks of a tile = words of an LDS row
+constexpr int kTrRows = 32 * kTrRb;       // source rows of a tile (128 bytes of an output row)
+constexpr int kTrGenes = 32 * kTrWords;
+constexpr int kTrPc = kTrRb / 4;          // 16-byte pieces of an output row per tile
+
+static_assert(kTrRb == 32 && kTrWords == 16, "tr_col's bank analysis is for LDS rows of 32 words, 16 words j per row block");
+__device__ __forceinline__ int tr_col(int g, int rb) { return (rb + 2 * (g >> 5) + (g & 3)) & 31; }
+
+// a[i] bit c <-> a[c] bit i: at scale j the blocks (rows without bit j, columns with it) and (rows
+// with bit j, columns without it) change places
+__device__ __forceinline__ void tr_32x32(uint32_t (&a)[32]) {
+#pragma unroll
+  for (int j = 16; j; j >>= 1) {
+    const uint32_t m = 0xffffffffu / ((1u << j) + 1u);  // the columns without bit j
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      if (k & j) continue;
+      const uint32_t t = ((a[k] >> j) ^ a[k + j]) & m;
+      a[k + j] ^= t;
+      a[k] ^= t << j;
+    }
+  }
+}
+
+// the 32 words of the lane's block: rows row .. row + 31 of word w. kEdge: a tile that reaches past the
+// n rows or the kw readable words of a row (loads clamped to the last valid row / word, then zeroed);
+// else the addresses are one lane base plus a uniform multiple of the pitch
+template <bool kEdge>
+__device__ __forceinline__ void tr_load(uint32_t (&a)[32], const uint8_t* __restrict__ bits, int64_t n, int64_t ldb,
+                                        int64_t kw, int64_t w, int64_t row) {
+  if (kEdge) {
+    const uint8_t* src = bits + min(w, kw - 1) * 4;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) a[i] = *(const uint32_t*)(src + min(row + i, n - 1) * ldb);
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+      if (!(w < kw && row + i < n)) a[i] = 0u;
+  } else {
+    const uint8_t* src = bits + row * ldb + w * 4;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) a[i] = *(const uint32_t*)(src + i * ldb);
+  }
+}
+
+// Tiles in a 1-D grid, in bands of kTrBand gene tiles: inside a band the gene tiles run fastest, then
+// the row tiles, so the few hundred workgroups in flight together read kTrBand * kTrWords * 4
+// contiguous bytes of each of their rows and write neighbouring lines of the same gene rows (gene tiles
+// fastest over the whole width had every 128-byte store of a moment on a line of its own row,
+// roundup(n, 128) / 8 bytes from the next: 7.4 ms against 4.0 ms at 1e6 x 55,039; bands of 8 and of 32
+// measured 3-6 % slower than 16)
+constexpr int kTrBand = 16;
+__global__ __launch_bounds__(kTrThreads) void k_bit_transpose(const uint8_t* __restrict__ bits, int64_t n, int64_t ldb,
+                                                            int64_t kw, int64_t G, uint8_t* __restrict__ out,
+                                                            int64_t ldo, int64_t ob, int tiles_g, int tiles_r) {
+  __shared__ __attribute__((aligned(16))) uint32_t lt[kTrGenes * kTrRb];
+  const int band = blockIdx.x / (kTrBand * tiles_r), in_band = blockIdx.x - band * (kTrBand * tiles_r);
+  const int band_tiles = min(kTrBand, tiles_g - band * kTrBand);  // (the last band may be narrower)
+  const int64_t r0 = (int64_t)(in_band / band_tiles) * kTrRows;
+  const int64_t w0 = (int64_t)(band * kTrBand + in_band % band_tiles) * kTrWords;
+  const int j = threadIdx.x & (kTrWords - 1), rb = threadIdx.x / kTrWords;
+  uint32_t a[32];
+  if (r0 + kTrRows <= n && w0 + kTrWords <= kw)  // (uniform over the workgroup)
+    tr_load<false>(a, bits, n, ldb, kw, w0 + j, r0 + 32 * rb);
+  else
+    tr_load<true>(a, bits, n, ldb, kw, w0 + j, r0 + 32 * rb);
+  tr_32x32(a);
+#pragma unroll
+  for (int b = 0; b < 32; ++b) lt[(32 * j + b) * kTrRb + tr_col(32 * j + b, rb)] = a[b];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kTrGenes * kTrPc / kTrThreads; ++k) {
+    const int p = threadIdx.x + kTrThreads * k, g = p / kTrPc, q = p % kTrPc;
+    const uint32_t* lr = lt + g * kTrRb;
+    const uint4 v = make_uint4(lr[tr_col(g, 4 * q)], lr[tr_col(g, 4 * q + 1)], lr[tr_col(g, 4 * q + 2)],
+                               lr[tr_col(g, 4 * q + 3)]);
+    const int64_t gene = w0 * 32 + g, byte = r0 / 8 + 16 * q;
+    if (gene < G && byte < ob) {  // (ob: the bytes of an output row that are written, a multiple of 16)
+      GM2_DBG(gene >= 0 && gene < G && byte >= 0 && byte + 16 <= (n + 127) / 128 * 16 && byte + 16 <= ldo, kDbgTranspose);
+      *(uint4*)(out + gene * ldo + byte) = v;
+    }
+  }
+}
+
 // 1-D grid of ta x tb tiles
 unsigned bit_grid(int64_t ra, int64_t rb, int* tiles_b) {
   const int64_t ta = (ra + kBgTile - 1) / kBgTile, tb = (rb + kBgTile - 1) / kBgTile;
@@ -567,6 +674,19 @@ void launch_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ldb, int64_
   else
     hipLaunchKernelGGL(k_gene_counts<false>, grid, dim3(256), 0, s, bits, n_rows, ldb, (int)nw, G, rows, n, slab_rows,
                        (int)nc, (unsigned long long*)counts);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_bit_transpose(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G, uint8_t* out, int64_t ldo,
+                          hipStream_t s) {
+  if (n <= 0) return;
+  const int64_t tr = (n + kTrRows - 1) / kTrRows, tg = (G + kTrGenes - 1) / kTrGenes;
+  if (tr * tg > 0x7fffffff)
+    throw Gm2Error("mask_transpose: %lld rows x %lld genes are more tiles than one launch holds", (long long)n,
+                   (long long)G);
+  const int64_t kw = (G + 127) / 128 * 4, ob = (n + 127) / 128 * 16;
+  hipLaunchKernelGGL(k_bit_transpose, dim3((unsigned)(tr * tg)), dim3(kTrThreads), 0, s, bits, n, ldb, kw, G, out, ldo,
+                     ob, (int)tg, (int)tr);
   GM2_CHECK_LAUNCH();
 }
 

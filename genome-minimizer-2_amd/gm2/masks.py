@@ -107,6 +107,49 @@ class PackedMasks:
         key = best.cpu().numpy()
         return key >> 32, key & 0xFFFFFFFF
 
+    def transposed(self):
+        """The gene-major set: a PackedMasks of G rows x n "genes", row g = the genomes that carry gene
+        g as a packed bit row (gm2_mask_transpose, on the device)."""
+        if self.n == 0:
+            raise ValueError("transposed: no rows to transpose (n = 0)")
+        ld = native.packed_row_bytes(self.n)
+        out = torch.zeros(self.G, ld, dtype=torch.uint8, device=self.bits.device)
+        native.mask_transpose(self.bits, self.n, self.ld, self.G, out, ld)
+        return PackedMasks(out, self.n)
+
+    def _gene_list(self, genes):
+        """A column index array -> device int64 indices for index_select (None: every gene). Host
+        arrays are range-checked as _row_list does; a device tensor's entries are index_select's."""
+        dev = self.bits.device
+        if genes is None:
+            return None
+        if isinstance(genes, torch.Tensor):
+            return genes.reshape(-1).to(device=dev, dtype=torch.int64)
+        g = np.asarray(genes)
+        if g.size == 0:
+            g = np.zeros(0, dtype=np.int64)
+        elif g.ndim != 1 or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("gene_cooccurrence: genes must be a 1-D integer index array")
+        if g.size and (g.min() < 0 or g.max() >= self.G):
+            raise ValueError(f"gene_cooccurrence: gene indices outside [0, {self.G})")
+        return torch.from_numpy(g.astype(np.int64)).to(dev)
+
+    def gene_cooccurrence(self, genes=None, other_genes=None, transposed=None):
+        """Genomes that carry both gene a and gene b -> device int32 [Ka, Kb] (the Gram matrix X^T X
+        restricted to the chosen columns). genes / other_genes: integer column index arrays, repeats
+        allowed, None = every gene; other_genes None = genes. transposed: this set's transposed() when
+        the caller already holds it, else it is formed here."""
+        t = self.transposed() if transposed is None else transposed
+        if t.n != self.G or t.G != self.n:
+            raise ValueError(f"gene_cooccurrence: a transposed set of {t.n} rows x {t.G} for {self.n} x {self.G}")
+        ia = self._gene_list(genes)
+        ib = ia if other_genes is None else self._gene_list(other_genes)
+        a = t if ia is None else PackedMasks(t.bits.index_select(0, ia), t.G)
+        if other_genes is None:
+            return a.cooccurrence()
+        b = t if ib is None else PackedMasks(t.bits.index_select(0, ib), t.G)
+        return a.cooccurrence(b)
+
     def _row_list(self, rows):
         """An index array or a boolean mask of length n -> device int32 indices. Host arrays are
         range-checked here; a device tensor's entries are the caller's (the debug build checks them)."""

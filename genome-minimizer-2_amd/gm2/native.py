@@ -38,7 +38,7 @@ EXPORTS = ["gm2_last_error", "gm2_abi_version", "gm2_param_count", "gm2_param_of
            "gm2_resident_layout", "gm2_resident_build",
            "gm2_timing_begin", "gm2_timing_end", "gm2_timing_class", "gm2_workspace_stat",
            "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand",
-           "gm2_mask_cooccur", "gm2_mask_nearest", "gm2_mask_gene_counts"]
+           "gm2_mask_cooccur", "gm2_mask_nearest", "gm2_mask_gene_counts", "gm2_mask_transpose"]
 ABI_VERSION = 6
 KC_RECON_LOSS, KC_GEMM_STORE, KC_MASK, KC_ADAM = 1, 2, 4, 8
 OPT_GEMM_PP, OPT_SIDE_STREAM, OPT_RECON_TILE, OPT_SMALL_SPLIT, OPT_BN_EPILOGUE, OPT_SMALL_WAVES = 1, 2, 3, 4, 5, 6
@@ -116,6 +116,7 @@ def lib():
         "gm2_mask_cooccur": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, vp, i64, vp]),
         "gm2_mask_nearest": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, vp, vp]),
         "gm2_mask_gene_counts": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i32, vp]),
+        "gm2_mask_transpose": (C.c_int, [vp, i64, i64, i64, vp, i64, vp]),
         "gm2_recon_counts": (C.c_int, [dp, i32, C.POINTER(Batch), vp, vp, C.c_float, vp, vp, vp]),
         "gm2_gemm": (C.c_int, [i32, i32, i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, vp]),
         "gm2_grad_bucket_bounds": (C.c_int, [dp, C.POINTER(C.c_int64)]),
@@ -399,6 +400,12 @@ def mask_gene_counts(bits, n_rows, ld_bits, G, rows, n, counts, accumulate=False
     added to when `accumulate`, else overwritten) over packed rows (gm2_mask_gene_counts)."""
     check(lib().gm2_mask_gene_counts(ptr(bits), int(n_rows), int(ld_bits), int(G), ptr(rows), int(n), ptr(counts),
                                      int(bool(accumulate)), stream()), "gm2_mask_gene_counts")
+
+
+def mask_transpose(bits, n, ld_bits, G, out, ld_out):
+    """out [G][ld_out] = the bit transpose of the packed rows bits [n][ld_bits] (gm2_mask_transpose)."""
+    check(lib().gm2_mask_transpose(ptr(bits), int(n), int(ld_bits), int(G), ptr(out), int(ld_out), stream()),
+          "gm2_mask_transpose")
 
 
 def recon_counts(ws: Workspace, batch: Batch, params, bn, threshold, counts):

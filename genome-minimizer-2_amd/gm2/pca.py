@@ -17,6 +17,14 @@ C = X X^T = popcount(x_i AND x_j), which gm2_mask_cooccur computes exactly on th
     = (C(P, X) - 1 r^T) U / sqrt(lambda): the two terms with 1^T U vanish, mu^T X^T = r^T. C(P, X) is
     the cross co-occurrence, taken in row chunks so that a million samples never hold an n x S matrix.
 
+For n >> G (a large sampled set) the n x n matrix does not fit and the same axes come from the gene
+side (side="genes"): the G x G counts C' = X^T X are the co-occurrence of the transposed packed rows
+(PackedMasks.transposed, gm2_mask_transpose: row g = the genomes of gene g), c = diag C' the genes'
+counts, and the scatter matrix of the centred data is S = Xc^T Xc = C' - c c^T / n. S = V diag(lambda) V^T
+has the same non-zero lambda as K and its eigenvectors are the axes themselves, so the sign rule applies
+to V directly and the scores of any rows P are (P - 1 mu^T) V = P V - mu^T V with mu = c / n; P V is
+_xt_u of P's transposed rows. side="auto" keeps the strains side whenever its buffers fit.
+
 Everything after the integer counts is fp64 torch on the device the counts live on (the GPU for
 PackedMasks, the CPU for a numpy Gram source): the eigenproblem is n x n and not a hot path.
 """
@@ -66,14 +74,29 @@ def _xt_u(x, u, chunk=1024):
     return torch.cat(out)
 
 
+def _transposed(x):
+    """The gene-major view: PackedMasks.transposed() on the device, `x.T` of a host array."""
+    return x.transposed() if isinstance(x, PackedMasks) else np.ascontiguousarray(np.asarray(x).T)
+
+
+SIDES = ("auto", "strains", "genes")
+
+
 class BinaryPCA:
     """PCA(n_components) of 0/1 rows, sklearn's attributes and sign convention, from integer counts.
+
+    side: "strains" fits from the n x n counts of the rows, "genes" from the G x G counts of the
+    transposed rows (the same PCA; for n >> G), "auto" the strains side whenever its device buffers fit
+    and the genes side only where they do not.
 
     gram(a, b=None) -> the counts popcount(a_i AND b_j) as an integer array (numpy or torch; b None =
     a with itself) of whatever fit / transform are given: the default takes PackedMasks through
     gm2_mask_cooccur; numpy_gram takes host 0/1 arrays. There is no host fallback for PackedMasks."""
 
-    def __init__(self, n_components=2, gram=None, transform_rows=16384):
+    def __init__(self, n_components=2, gram=None, transform_rows=16384, side="auto"):
+        if side not in SIDES:
+            raise ValueError(f"BinaryPCA: side={side!r} is not one of {SIDES}")
+        self.side = side
         self.n_components = int(n_components)
         self.gram = gram or packed_gram
         self.transform_rows = int(transform_rows)
@@ -93,13 +116,26 @@ class BinaryPCA:
         k = self.n_components
         if k < 1 or k > min(n, G):
             raise ValueError(f"n_components={k} must be between 1 and min(n_samples, n_features)={min(n, G)}")
+        side = "strains" if self.side == "auto" else self.side
         if isinstance(x, PackedMasks) and x.bits.is_cuda:
-            # C (int32), K and its eigenvectors (fp64) plus the solver's workspace, all n x n
+            # C (int32), K and its eigenvectors (fp64) plus the solver's workspace, all n x n; on the
+            # gene side the same G x G, plus the transposed rows
             need, free = 36 * n * n, torch.cuda.mem_get_info(x.bits.device)[0]
-            if need > free:
+            need_g = 36 * G * G + G * ((n + 127) // 128 * 16)
+            if self.side == "auto" and need > free:
+                side = "genes"
+            if side == "strains" and need > free:
                 raise MemoryError(f"BinaryPCA: the {n} x {n} int32 and fp64 buffers need {need / 2**30:.1f} GiB, "
-                                  f"{free / 2**30:.1f} GiB of device memory are free (gene-side PCA for "
-                                  f"n >> G = {G} is not implemented)")
+                                  f"{free / 2**30:.1f} GiB of device memory are free (side='genes' fits from "
+                                  f"the {G} x {G} counts instead)")
+            if side == "genes" and need_g > free:
+                raise MemoryError(f"BinaryPCA: the {G} x {G} gene-side buffers need {need_g / 2**30:.1f} GiB"
+                                  + (f" and the {n} x {n} strain-side buffers {need / 2**30:.1f} GiB"
+                                     if self.side == "auto" else "")
+                                  + f", {free / 2**30:.1f} GiB of device memory are free")
+        self.side_ = side
+        if side == "genes":
+            return self._fit_genes(x, n, G, k)
         K = self._counts(x).to(torch.float64)
         r = K.mean(dim=1)
         K -= r[:, None]
@@ -122,11 +158,36 @@ class BinaryPCA:
         self.explained_variance_ratio_ = (lam / total).cpu().numpy()
         return (self._U * self._sqrt_lam).cpu().numpy()
 
+    def _fit_genes(self, x, n, G, k):
+        xt = _transposed(x)
+        S = self._counts(xt).to(torch.float64)
+        c = torch.diagonal(S).clone()
+        S -= c[:, None] * (c[None, :] / n)
+        total = torch.diagonal(S).sum()
+        lam, V = torch.linalg.eigh(S)
+        lam, V = lam[-k:].flip(0).clamp_min(0.0), V[:, -k:].flip(1)
+        top = V.abs().argmax(dim=0)
+        sign = torch.sign(V[top, torch.arange(k, device=V.device)])
+        sign[sign == 0] = 1.0
+        self._V = V * sign
+        self._mean_v = (c / n) @ self._V
+        self.n_samples_, self.n_features_in_ = n, G
+        self.singular_values_ = lam.sqrt().cpu().numpy()
+        self.explained_variance_ = (lam / max(n - 1, 1)).cpu().numpy()
+        self.explained_variance_ratio_ = (lam / total).cpu().numpy()
+        return (_xt_u(xt, self._V) - self._mean_v).cpu().numpy()
+
     def transform(self, other):
         """Scores of other rows on the fitted axes -> fp64 numpy [rows, n_components]."""
         m, G = _shape(other)
         if G != self.n_features_in_:
             raise ValueError(f"transform: {G} genes, fitted on {self.n_features_in_}")
+        if self.side_ == "genes":
+            out = np.empty((m, self.n_components), dtype=np.float64)
+            for lo in range(0, m, self.transform_rows):
+                hi = min(m, lo + self.transform_rows)
+                out[lo:hi] = (_xt_u(_transposed(_rows(other, lo, hi)), self._V) - self._mean_v).cpu().numpy()
+            return out
         proj = self._U / self._sqrt_lam
         out = np.empty((m, self.n_components), dtype=np.float64)
         for lo in range(0, m, self.transform_rows):

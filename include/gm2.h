@@ -264,6 +264,22 @@ int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* r
 int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, int64_t G, const int32_t* rows,
                          int64_t n, int64_t* counts, int accumulate, void* stream);
 
+/* (ABI 6, additive) out [G][ld_out] = the bit transpose of bits [n][ld_bits]: bit (i & 7) of byte i / 8
+ * of out row g = bit (g & 7) of byte g / 8 of bits row i. Same packed layout on both sides, so out is
+ * a packed row set of G rows x n "genes" (the strains of one gene as a bit row: gm2_mask_cooccur on it
+ * gives gene x gene counts).
+ * bits: the packed layout above (pitch a multiple of 16 covering G, rows 16-B aligned); only the first
+ * roundup(G,128)/8 bytes of a row are ever read. out: 16-B aligned, ld_out a multiple of 16 with
+ * ld_out * 8 >= n; exactly bytes [0, gm2_packed_row_bytes(n)) of each of the G rows are written, bits at
+ * positions >= n as zero; bytes of a row beyond that extent and every row >= G are not touched. out
+ * must not overlap bits. 1 <= G <= 2^31-1, 0 <= n <= 2^31-1.
+ * Stream-ordered, no allocation, no atomics: one launch, every byte read and written once.
+ * Return < 0 (see the last-error message) on a negative n, G < 1, a bad pitch or alignment on either
+ * side, out == NULL, overlapping byte ranges, or more tiles than one launch holds. n == 0 returns 0
+ * with no launch and writes nothing. */
+int gm2_mask_transpose(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, uint8_t* out, int64_t ld_out,
+                       void* stream);
+
 /* calculate_reconstruction_metrics (training/evaluation/metrics.py:19-64) without materialising the
  * reconstruction: eval-mode model(x) of `batch` (eps given: the reference samples z there too), then
  * per strain counts[i] = (TP, FP, FN) of (recon > threshold) against the strain's genes. */

@@ -26,6 +26,7 @@ extern "C" {
 #define GM2_DBG_BAND_BLOCK 128   /* sampling decode: a band-overflow block (or their count) outside the block grid */
 #define GM2_DBG_BIT_ROWS 256     /* gm2_mask_cooccur / gm2_mask_nearest: a store outside out / a winner outside [0, nr) */
 #define GM2_DBG_GENE_ROWS 512    /* gm2_mask_gene_counts: an index-list entry outside [0, n_rows) */
+#define GM2_DBG_TRANSPOSE 1024   /* gm2_mask_transpose: a store outside the G rows x gm2_packed_row_bytes(n) bytes it writes */
 
 /* OR of the failed checks of every kernel since the last call, then cleared (waits for the device) */
 int gm2_debug_flags(unsigned* flags);

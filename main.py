@@ -37,7 +37,10 @@ strain of every sample by Hamming distance, and the PCA of the strains (the refe
 with the samples projected onto its axes. --gene-frequencies (sample mode, off by default) counts the
 genomes per gene of the sampled set and of the strains on the packed rows (gm2_mask_gene_counts,
 gm2/genefreq.py) and writes the real-vs-sampled frequency table, per phylogroup for the strains and,
-with --nearest-strains, for the samples by their nearest strain's phylogroup.
+with --nearest-strains, for the samples by their nearest strain's phylogroup. --gene-linkage (sample
+mode, off by default) compares which genes travel together: the gene x gene co-occurrence counts of a
+panel of --linkage-genes intermediate-frequency genes in the strains and in the samples, from the
+gene-major packed rows (gm2_mask_transpose, then gm2_mask_cooccur; gm2/linkage.py), as phi coefficients.
 """
 import argparse
 import os
@@ -78,6 +81,10 @@ def parse_arguments(argv=None):
                    help="sample mode: PCA of the dataset strains with the sampled genomes projected onto it (CSV, PDF)")
     p.add_argument("--gene-frequencies", action="store_true",
                    help="sample mode: per-gene frequency of the sampled genomes against the dataset strains (CSV)")
+    p.add_argument("--gene-linkage", action="store_true",
+                   help="sample mode: gene-gene linkage (phi) of the sampled genomes against the dataset strains (CSV)")
+    p.add_argument("--linkage-genes", type=int, default=2048,
+                   help="sample mode, --gene-linkage: the most genes of the linkage panel")
     p.add_argument("--genome-path", type=str, default=None,
                    help="GenBank genome (default: <project root>/data/wild_type_sequence.gb)")
     p.add_argument("--output-dir", type=str, default="./minimized_genomes")
@@ -197,9 +204,33 @@ def gene_frequencies(packed, real, merged, nearest_idx, path):
           f"{s['sampled_absent_from_real']}\n- Gene frequencies: {path}")
 
 
+def gene_linkage(packed, real, merged, k, path):
+    """--gene-linkage: the panel (at most k genes of intermediate frequency in the strains), its gene x
+    gene co-occurrence counts in the strains and in the samples (PackedMasks.gene_cooccurrence: both sets
+    are transposed and counted on the device, no mask crosses PCIe for it), then the phi table."""
+    from gm2 import genefreq, linkage
+    panel = linkage.select_panel(genefreq.gene_counts(real), real.n, k=k)
+    if len(panel) == 0:
+        print("- Gene linkage: no gene of the strains has a frequency between 5 % and 95 %: nothing to compare")
+        return
+    both_real = real.gene_cooccurrence(panel).cpu().numpy()
+    both_sampled = packed.gene_cooccurrence(panel).cpu().numpy()
+    c_real, c_sampled = both_real.diagonal(), both_sampled.diagonal()
+    table = linkage.linkage_table(merged.columns[:-1].to_numpy(), panel, both_real, c_real, real.n,
+                                  both_sampled, c_sampled, packed.n)
+    table.to_csv(path, index=False)
+    s = linkage.linkage_summary(linkage.phi_matrix(both_real, c_real, real.n),
+                                linkage.phi_matrix(both_sampled, c_sampled, packed.n))
+    print(f"- Gene linkage, sampled vs real, {len(panel)} genes, {s['pairs']} pairs: Pearson r {s['pearson_r']:.4f}, "
+          f"|delta phi| mean {s['mean_abs_delta']:.4f}, max {s['max_abs_delta']:.4f}")
+    print(f"- Strongly linked pairs of the strains (|phi| >= 0.5): {s['real_strong']}; kept in the samples: "
+          f"{s['real_strong_kept']}; strong in the samples only: {s['sampled_strong_new']}")
+    print(f"- Panel genes constant in the samples: {s['sampled_constant']}\n- Gene linkage: {path}")
+
+
 def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
-    """--nearest-strains / --pca / --gene-frequencies: the sampled genomes against the dataset's strains,
-    on the device."""
+    """--nearest-strains / --pca / --gene-frequencies / --gene-linkage: the sampled genomes against the
+    dataset's strains, on the device."""
     import numpy as np
     import pandas as pd
     from gm2.masks import PackedMasks
@@ -215,6 +246,8 @@ def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
         print(f"- Samples identical to a dataset strain: {int((ham == 0).sum())}\n- Nearest strains: {path}")
     if args.gene_frequencies:
         gene_frequencies(packed, real, merged, idx, out_dir / f"{tag}_gene_frequencies_{mode}.csv")
+    if args.gene_linkage:
+        gene_linkage(packed, real, merged, args.linkage_genes, out_dir / f"{tag}_gene_linkage_{mode}.csv")
     if args.pca:
         from gm2.pca import BinaryPCA
         pca = BinaryPCA(n_components=2)
@@ -317,7 +350,7 @@ def run_sampling(args):
     print(f"- Genome size range: {np.min(sizes):.0f} - {np.max(sizes):.0f}")
     print(f"- Median essential genes: {np.median(ess):.0f}")
     print(f"- Essential range: {np.min(ess):.0f} - {np.max(ess):.0f}")
-    if args.nearest_strains or args.pca or args.gene_frequencies:
+    if args.nearest_strains or args.pca or args.gene_frequencies or args.gene_linkage:
         compare_with_strains(args, packed, sizes, merged, out_dir, config.trainer_version)
     if args.mask_dtype == "bits":
         out = packed.to_host()

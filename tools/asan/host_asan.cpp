@@ -233,6 +233,19 @@ static void error_paths() {
   expect_error(gm2_mask_gene_counts(rows_a, 2, 16, 100, idx, 2, nullptr, 1, nullptr), "null", "gene_counts null counts");
   CHECK(gm2_mask_gene_counts(rows_a, 2, 16, 100, nullptr, 0, gc, 1, nullptr) == 0, "gene_counts of no rows, accumulating");
   CHECK(gm2_mask_gene_counts(rows_a, 2, 16, 100, idx, 0, gc, 1, nullptr) == 0, "gene_counts of an empty list, accumulating");
+  // bit transpose: 4 rows of 100 genes -> 100 rows of 4 bits; every refusal is host-side
+  alignas(16) static uint8_t tr_in[4 * 16], tr_out[100 * 16];
+  expect_error(gm2_mask_transpose(tr_in, -1, 16, 100, tr_out, 16, nullptr), "negative", "transpose n < 0");
+  expect_error(gm2_mask_transpose(tr_in, 4, 16, 0, tr_out, 16, nullptr), "G", "transpose G = 0");
+  expect_error(gm2_mask_transpose(tr_in, 4, 24, 100, tr_out, 16, nullptr), "pitch", "transpose ld_bits % 16");
+  expect_error(gm2_mask_transpose(tr_in, 4, 16, 129, tr_out, 16, nullptr), "pitch", "transpose pitch < G bits");
+  expect_error(gm2_mask_transpose(tr_in, 4, 16, 100, tr_out, 24, nullptr), "pitch", "transpose ld_out % 16");
+  expect_error(gm2_mask_transpose(tr_in, 129, 16, 100, tr_out, 16, nullptr), "pitch", "transpose ld_out * 8 < n");
+  expect_error(gm2_mask_transpose(tr_in + 8, 4, 16, 100, tr_out, 16, nullptr), "aligned", "transpose misaligned bits");
+  expect_error(gm2_mask_transpose(tr_in, 4, 16, 100, tr_out + 4, 16, nullptr), "aligned", "transpose misaligned out");
+  expect_error(gm2_mask_transpose(tr_in, 4, 16, 100, nullptr, 16, nullptr), "null", "transpose null out");
+  expect_error(gm2_mask_transpose(tr_out, 4, 16, 100, tr_out + 48, 16, nullptr), "overlap", "transpose out inside bits");
+  CHECK(gm2_mask_transpose(tr_in, 0, 16, 100, tr_out, 16, nullptr) == 0, "transpose of no rows");
   std::string last = gm2_last_error();
   CHECK(!last.empty(), "an error message is kept");
   unsigned flags = 1;
