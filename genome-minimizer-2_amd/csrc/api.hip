@@ -1663,6 +1663,32 @@ int gm2_mask_transpose(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t 
   });
 }
 
+int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, const int32_t* feat_col,
+                             const int32_t* feat_start, const int32_t* feat_end, int64_t F, int64_t* removed_bp,
+                             int32_t* genes_removed, uint64_t* signature, void* stream) {
+  return guarded([&] {
+    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_minimized_stats: G %lld outside [1, 2^31)", (long long)G);
+    if (F < 0 || F > 0x7fffffff) throw Gm2Error("mask_minimized_stats: F %lld outside [0, 2^31)", (long long)F);
+    check_bit_rows("mask_minimized_stats", "bits", bits, n, ld_bits, G);
+    if (((uintptr_t)feat_col | (uintptr_t)feat_start | (uintptr_t)feat_end) & 3)
+      throw Gm2Error("mask_minimized_stats: the feature tables must be 4-B aligned");
+    if (F && (!feat_col || !feat_start || !feat_end)) throw Gm2Error("mask_minimized_stats: null feature table");
+    if (((uintptr_t)removed_bp | (uintptr_t)signature) & 7)
+      throw Gm2Error("mask_minimized_stats: removed_bp and signature must be 8-B aligned");
+    if ((uintptr_t)genes_removed & 3) throw Gm2Error("mask_minimized_stats: genes_removed must be 4-B aligned");
+    if (n == 0) return;
+    if (!removed_bp || !genes_removed || !signature) throw Gm2Error("mask_minimized_stats: null output");
+    if (F == 0) {  // (no feature: nothing is removed)
+      HIP_OK(hipMemsetAsync(removed_bp, 0, (size_t)n * 8, (hipStream_t)stream));
+      HIP_OK(hipMemsetAsync(genes_removed, 0, (size_t)n * 4, (hipStream_t)stream));
+      HIP_OK(hipMemsetAsync(signature, 0, (size_t)n * 8, (hipStream_t)stream));
+      return;
+    }
+    launch_minimized_stats(bits, n, ld_bits, G, feat_col, feat_start, feat_end, F, removed_bp, genes_removed, signature,
+                           (hipStream_t)stream);
+  });
+}
+
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {

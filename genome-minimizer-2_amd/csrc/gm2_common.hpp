@@ -64,7 +64,8 @@ enum DebugBit : unsigned {
   kDbgResidentRows = 1u,   // k_resident_rows: rows[i] outside [0, S)
   kDbgGatherRows = 2u,     // k_gather: a negative row index
   kDbgGemmIdx = 4u,        // GEMM zero-copy row table: entry outside [0, idx_lim)
-  kDbgMaskPos = 8u,        // k_count_groups: group offsets not ascending / position outside the row
+  kDbgMaskPos = 8u,        // k_count_groups: group offsets not ascending / position outside the row;
+                           // k_minimized_stats: a feature column outside [-2, G)
   kDbgCompact = 16u,       // k_compact: an index written outside [off[row], off[row + 1])
   kDbgReconRows = 32u,     // loss epilogue: target-bit row outside [0, idx_lim)
   kDbgTile = 64u,          // a GEMM tile origin outside the padded operand extents

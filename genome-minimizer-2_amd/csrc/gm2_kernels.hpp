@@ -447,6 +447,14 @@ void launch_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ldb, int64_
 // read; out and bits 16-B aligned, pitches multiples of 16, no overlap; n > 0 launches
 void launch_bit_transpose(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G, uint8_t* out, int64_t ldo,
                           hipStream_t s);
+// minimized genome sizes: per row i < n of bits [n][ldb] the removed gene features of a record given as
+// F features sorted by start (fcol >= 0: kept iff that bit is set, -1: removed, -2: kept; [fstart, fend)):
+// removed_bp[i] = bases of the union of the removed non-empty intervals, genes_removed[i] = removed
+// features, signature[i] = sum over the merged removed intervals of mix(2 start) + mix(2 end + 1). The
+// first roundup(G, 128) / 8 bytes of a row are read; bits 16-B aligned, ldb a multiple of 16; n > 0 launches
+void launch_minimized_stats(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G, const int32_t* fcol,
+                            const int32_t* fstart, const int32_t* fend, int64_t F, int64_t* removed_bp,
+                            int32_t* genes_removed, uint64_t* signature, hipStream_t s);
 
 // parameter tensor table for the multi-tensor optimizer / shadow kernels
 struct TensorDesc {

@@ -9,6 +9,10 @@
 //     matrix of 0/1 rows, and the nearest row by popcount(a XOR b). VALU-bound, LDS-tiled.
 //   * genomes per gene (explore_data/data_exploration.py:119-120, `sum(axis=0)` of the 0/1 matrix):
 //     the column sums of the bit rows on bit-sliced carry-save counters, every row byte read once.
+//   * the genome minimizer's sizes (minimizer/minimizer_2.py:50-101, :273-424): per sample, the gene
+//     features it removes from the GenBank record, the bases their union covers and a signature of the
+//     merged removed regions (equal signature = the same minimized sequence), from a bit gather per
+//     feature and a prefix-max scan over the features sorted by start.
 // Mask rows are numpy packbits(bitorder='little') bytes: bit (g & 7) of byte g / 8 = gene g,
 // row pitch ld_bits (multiple of 16 bytes), bits beyond G zero. The first two are HBM-bound integer
 // work: their kernels stream each mask row once with 16-byte (or 4-byte word) loads.
@@ -620,6 +624,114 @@ __global__ __launch_bounds__(kTrThreads) void k_bit_transpose(const uint8_t* __r
   }
 }
 
+// ---- minimized genome sizes: what GenomeMinimiser (minimizer/minimizer_2.py:50-101) would cut from the
+// GenBank record for each sampled row, without the sequence ----
+// The record's gene features arrive sorted by start as three int32 tables: col (>= 0: the feature is
+// kept iff that bit of the row is set; -1: always removed; -2: always kept), start and end ([start, end)
+// clipped to the record). Per row: the number of removed features, the length of the union of the
+// removed non-empty intervals, and a 64-bit signature of the merged intervals (the sum over them of
+// mix(2 start) + mix(2 end + 1), mix = the splitmix64 finalizer; integer adds commute, so the order of
+// the reduction does not matter). One wave per row, kMsRowsPerWg rows per workgroup; the wave first
+// copies its row into LDS (16-byte loads, every row byte read once) when four rows fit in 64 KB, and the
+// per-feature bit gathers go there. The features are walked in chunks of 64, feature = chunk * 64 + lane
+// (coalesced table loads, the next chunk's in flight under this one's scan; the tables stay in L2). With
+// the starts ascending, the merged intervals follow from a running maximum: cover = the largest end of the
+// removed non-empty features before this one = max(wave-uniform carry of the earlier chunks, exclusive
+// prefix max over the lanes). The feature adds max(0, end - max(start, cover)) bases; it opens a new
+// interval iff start > cover (touching intervals merge), and then cover, if any, closed the one before;
+// the last interval's end is the carry after the last chunk.
+constexpr int kMsRowsPerWg = 16;
+
+__device__ __forceinline__ unsigned long long ms_mix(unsigned long long z) {
+  z ^= z >> 30;
+  z *= 0xbf58476d1ce4e5b9ull;
+  z ^= z >> 27;
+  z *= 0x94d049bb133111ebull;
+  z ^= z >> 31;
+  return z;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// inclusive prefix max over the wave's 64 lanes of values >= -1 (the identity), on the DPP lane routes:
+// shifts by 1, 2, 4, 8 inside each row of 16 lanes (a lane without a source keeps the identity), then
+// lane 15 of rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 and 3. Six full-rate VALU pairs; the
+// same scan with __shfl_up is six ds_bpermute round trips through the LDS crossbar, each waited for.
+__device__ __forceinline__ int wave_scan_max(int v) {
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x111, 0xf, 0xf, false));  // row_shr:1
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x112, 0xf, 0xf, false));  // row_shr:2
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x114, 0xf, 0xf, false));  // row_shr:4
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x118, 0xf, 0xf, false));  // row_shr:8
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x142, 0xa, 0xf, false));  // row_bcast:15 -> rows 1, 3
+  v = max(v, __builtin_amdgcn_update_dpp(-1, v, 0x143, 0xc, 0xf, false));  // row_bcast:31 -> rows 2, 3
+  return v;
+}
+
+template <bool kStage>
+__global__ __launch_bounds__(256) void k_minimized_stats(const uint8_t* __restrict__ bits, int64_t n, int64_t ldb, int kb16,
+                                                       int G, const int32_t* __restrict__ fcol,
+                                                       const int32_t* __restrict__ fstart,
+                                                       const int32_t* __restrict__ fend, int F,
+                                                       int64_t* __restrict__ removed_bp, int32_t* __restrict__ genes_removed,
+                                                       unsigned long long* __restrict__ signature) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t ms_rows[];  // kStage: [4 waves][kb16 * 16 bytes]
+  const int lane = threadIdx.x & 63;
+  uint8_t* wrow = ms_rows + (size_t)(threadIdx.x >> 6) * kb16 * 16;
+  const int64_t r1 = min(n, (int64_t)(blockIdx.x + 1) * kMsRowsPerWg);
+  for (int64_t row = (int64_t)blockIdx.x * kMsRowsPerWg + (threadIdx.x >> 6); row < r1; row += 4) {
+    const uint8_t* rb = bits + row * ldb;
+    if (kStage) {
+      for (int i = lane; i < kb16; i += 64) ((uint4*)wrow)[i] = ((const uint4*)rb)[i];
+      // (this wave's row writes, visible to its own lanes' reads below)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+    int carry = -1, gone = 0;  // carry: the largest removed non-empty end of the chunks so far (uniform)
+    unsigned long long bp = 0ull, sig = 0ull;
+    // (lanes beyond F hold an always-kept feature)
+    int c = -2, s = 0, e = 0;
+    if (lane < F) c = fcol[lane], s = fstart[lane], e = fend[lane];
+    for (int64_t f0 = 0; f0 < F; f0 += 64) {
+      int cn = -2, sn = 0, en = 0;
+      if (f0 + 64 + lane < F) cn = fcol[f0 + 64 + lane], sn = fstart[f0 + 64 + lane], en = fend[f0 + 64 + lane];
+      GM2_DBG(c >= -2 && c < G && (int64_t)(c >> 3) < ldb, kDbgMaskPos);
+      bool kept = c == -2;
+      if (c >= 0 && c < G) {  // (a column outside the row is never read: the feature counts as removed)
+        const int byte = kStage ? wrow[c >> 3] : rb[c >> 3];
+        kept = (byte >> (c & 7)) & 1;
+      }
+      const bool cut = !kept && e > s;  // a removed feature that covers bases
+      gone += !kept;
+      const int incl = wave_scan_max(cut ? e : -1);
+      // (wave_shr:1: the lane before's inclusive max, -1 in lane 0)
+      const int cover = max(carry, __builtin_amdgcn_update_dpp(-1, incl, 0x138, 0xf, 0xf, false));
+      carry = max(carry, __builtin_amdgcn_readlane(incl, 63));
+      if (cut) {
+        bp += (unsigned long long)max(0, e - max(s, cover));
+        if (s > cover) {
+          sig += ms_mix(2ull * (unsigned long long)(unsigned)s);
+          if (cover >= 0) sig += ms_mix(2ull * (unsigned long long)(unsigned)cover + 1ull);
+        }
+      }
+      c = cn, s = sn, e = en;
+    }
+    if (lane == 0 && carry >= 0) sig += ms_mix(2ull * (unsigned long long)(unsigned)carry + 1ull);
+    if (kStage) __builtin_amdgcn_wave_barrier();  // (the next row overwrites the buffer after these reads)
+    bp = wave_sum_u64(bp);
+    sig = wave_sum_u64(sig);
+    gone = wave_sum_i(gone);
+    if (lane == 0) {
+      removed_bp[row] = (int64_t)bp;
+      genes_removed[row] = gone;
+      signature[row] = sig;
+    }
+  }
+}
+
 // 1-D grid of ta x tb tiles
 unsigned bit_grid(int64_t ra, int64_t rb, int* tiles_b) {
   const int64_t ta = (ra + kBgTile - 1) / kBgTile, tb = (rb + kBgTile - 1) / kBgTile;
@@ -687,6 +799,24 @@ void launch_bit_transpose(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G
   const int64_t kw = (G + 127) / 128 * 4, ob = (n + 127) / 128 * 16;
   hipLaunchKernelGGL(k_bit_transpose, dim3((unsigned)(tr * tg)), dim3(kTrThreads), 0, s, bits, n, ldb, kw, G, out, ldo,
                      ob, (int)tg, (int)tr);
+  GM2_CHECK_LAUNCH();
+}
+
+void launch_minimized_stats(const uint8_t* bits, int64_t n, int64_t ldb, int64_t G, const int32_t* fcol,
+                            const int32_t* fstart, const int32_t* fend, int64_t F, int64_t* removed_bp,
+                            int32_t* genes_removed, uint64_t* signature, hipStream_t s) {
+  if (n <= 0) return;
+  const int64_t kb16 = (G + 127) / 128, wgs = (n + kMsRowsPerWg - 1) / kMsRowsPerWg;
+  if (wgs > 0x7fffffff)
+    throw Gm2Error("mask_minimized_stats: %lld rows are more workgroups than one launch holds", (long long)n);
+  // (each wave's row in LDS when the four of a workgroup fit in 64 KB; else the gathers read global memory)
+  const int64_t lds = 4 * kb16 * 16;
+  if (lds <= 64 * 1024)
+    hipLaunchKernelGGL(k_minimized_stats<true>, dim3((unsigned)wgs), dim3(256), (unsigned)lds, s, bits, n, ldb, (int)kb16,
+                       (int)G, fcol, fstart, fend, (int)F, removed_bp, genes_removed, (unsigned long long*)signature);
+  else
+    hipLaunchKernelGGL(k_minimized_stats<false>, dim3((unsigned)wgs), dim3(256), 0, s, bits, n, ldb, (int)kb16, (int)G,
+                       fcol, fstart, fend, (int)F, removed_bp, genes_removed, (unsigned long long*)signature);
   GM2_CHECK_LAUNCH();
 }
 

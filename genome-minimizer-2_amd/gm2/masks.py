@@ -11,6 +11,9 @@ consumers run on it without leaving the device:
     and the genes-in-at-least-t-genomes curve built on it (:213-230)
                                                           -> PackedMasks.gene_counts / gene_counts_by
                                                              (tables and summaries: gm2/genefreq.py)
+  * the minimizer's sizes and duplicate groups (minimizer/minimizer_2.py:50-101, :273-424) without
+    the sequences                                         -> PackedMasks.minimized_stats
+                                                             (plan, oracle, report: gm2/minsizes.py)
 and `to_host` returns the packed rows (8x less PCIe than u8) for the .npy writers.
 """
 from __future__ import annotations
@@ -223,6 +226,26 @@ class PackedMasks:
         po = torch.from_numpy(pos if len(pos) else np.zeros(1, np.int32)).to(dev)
         native.mask_count_groups(self.bits, self.n, self.ld, go, len(offs) - 1, po, counts)
         return counts.cpu().numpy().astype(np.int64)
+
+    def minimized_stats(self, plan):
+        """What the genome minimizer would cut from the plan's GenBank record for every row, without the
+        sequences (gm2.minsizes.FeaturePlan; gm2_mask_minimized_stats on the device) -> a dict of host
+        arrays [n]: removed_bp, genes_removed, reduced_length (int64) and signature (uint64; equal for rows
+        with the same merged removed regions). The same outputs as minsizes.minimized_stats_numpy."""
+        if plan.G != self.G:
+            raise ValueError(f"minimized_stats: a plan of {plan.G} gene columns for masks of {self.G}")
+        if self.n == 0:
+            from .minsizes import _empty_stats
+            return _empty_stats()
+        dev = self.bits.device
+        bp = torch.empty(self.n, dtype=torch.int64, device=dev)
+        gone = torch.empty(self.n, dtype=torch.int32, device=dev)
+        sig = torch.empty(self.n, dtype=torch.int64, device=dev)   # (the uint64's bytes)
+        col, start, end = plan.device_tables(dev) if plan.F else (None, None, None)
+        native.mask_minimized_stats(self.bits, self.n, self.ld, self.G, col, start, end, plan.F, bp, gone, sig)
+        removed = bp.cpu().numpy()
+        return {"removed_bp": removed, "genes_removed": gone.cpu().numpy().astype(np.int64),
+                "reduced_length": plan.L - removed, "signature": sig.cpu().numpy().view(np.uint64)}
 
     def _keep(self, keep_cols):
         if keep_cols is None:

@@ -38,7 +38,8 @@ EXPORTS = ["gm2_last_error", "gm2_abi_version", "gm2_param_count", "gm2_param_of
            "gm2_resident_layout", "gm2_resident_build",
            "gm2_timing_begin", "gm2_timing_end", "gm2_timing_class", "gm2_workspace_stat",
            "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand",
-           "gm2_mask_cooccur", "gm2_mask_nearest", "gm2_mask_gene_counts", "gm2_mask_transpose"]
+           "gm2_mask_cooccur", "gm2_mask_nearest", "gm2_mask_gene_counts", "gm2_mask_transpose",
+           "gm2_mask_minimized_stats"]
 ABI_VERSION = 6
 KC_RECON_LOSS, KC_GEMM_STORE, KC_MASK, KC_ADAM = 1, 2, 4, 8
 OPT_GEMM_PP, OPT_SIDE_STREAM, OPT_RECON_TILE, OPT_SMALL_SPLIT, OPT_BN_EPILOGUE, OPT_SMALL_WAVES = 1, 2, 3, 4, 5, 6
@@ -117,6 +118,7 @@ def lib():
         "gm2_mask_nearest": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, vp, vp]),
         "gm2_mask_gene_counts": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i32, vp]),
         "gm2_mask_transpose": (C.c_int, [vp, i64, i64, i64, vp, i64, vp]),
+        "gm2_mask_minimized_stats": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
         "gm2_recon_counts": (C.c_int, [dp, i32, C.POINTER(Batch), vp, vp, C.c_float, vp, vp, vp]),
         "gm2_gemm": (C.c_int, [i32, i32, i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, vp]),
         "gm2_grad_bucket_bounds": (C.c_int, [dp, C.POINTER(C.c_int64)]),
@@ -406,6 +408,16 @@ def mask_transpose(bits, n, ld_bits, G, out, ld_out):
     """out [G][ld_out] = the bit transpose of the packed rows bits [n][ld_bits] (gm2_mask_transpose)."""
     check(lib().gm2_mask_transpose(ptr(bits), int(n), int(ld_bits), int(G), ptr(out), int(ld_out), stream()),
           "gm2_mask_transpose")
+
+
+def mask_minimized_stats(bits, n, ld_bits, G, feat_col, feat_start, feat_end, F, removed_bp, genes_removed, signature):
+    """Per packed row, what the genome minimizer removes from a record of F gene features sorted by start
+    (int32 tables: feat_col >= 0 kept iff that bit is set, -1 removed, -2 kept; [feat_start, feat_end)):
+    removed_bp (int64 [n]), genes_removed (int32 [n]) and the signature of the merged removed intervals
+    (8 bytes per row, uint64) (gm2_mask_minimized_stats)."""
+    check(lib().gm2_mask_minimized_stats(ptr(bits), int(n), int(ld_bits), int(G), ptr(feat_col), ptr(feat_start),
+                                         ptr(feat_end), int(F), ptr(removed_bp), ptr(genes_removed), ptr(signature),
+                                         stream()), "gm2_mask_minimized_stats")
 
 
 def recon_counts(ws: Workspace, batch: Batch, params, bn, threshold, counts):

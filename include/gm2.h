@@ -280,6 +280,28 @@ int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, i
 int gm2_mask_transpose(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, uint8_t* out, int64_t ld_out,
                        void* stream);
 
+/* (ABI 6, additive) What the genome minimizer (minimizer/minimizer_2.py:50-101) would cut from one GenBank
+ * record for each of the n packed rows, without the sequence. The record's F gene features are three
+ * int32 device tables sorted by feat_start ascending, 0 <= feat_start, feat_end < 2^31, the interval
+ * [feat_start, feat_end) (empty when feat_end <= feat_start). feat_col[f] >= 0 (< G): the feature is kept
+ * iff that bit of the row is set; -1: always removed; -2: always kept. Per row i:
+ *   genes_removed[i] (int32) = the removed features, empty ones included;
+ *   removed_bp[i] (int64)    = the bases of the union of the removed non-empty intervals;
+ *   signature[i] (uint64)    = sum mod 2^64, over that union's maximal intervals [s, e) (touching
+ *     intervals merge), of mix(2 s) + mix(2 e + 1), mix the splitmix64 finalizer; 0 when nothing is
+ *     removed. Rows with equal signatures have the same removed regions, hence the same minimized
+ *     sequence (up to 2^-64 collisions).
+ * bits: the packed layout above (pitch a multiple of 16 covering G, rows 16-B aligned); only the first
+ * roundup(G,128)/8 bytes of a row are read. A feat_col outside [-2, G) is never used as an index: its
+ * feature counts as removed (the debug build flags it as GM2_DBG_MASK_POS). Exactly n elements of each
+ * output are written. Stream-ordered, no allocation, no atomics: one launch, every row byte read once.
+ * Return < 0 (see the last-error message) on a negative n, G < 1, F < 0, a bad pitch or alignment, a null
+ * table with F > 0 or a null output with n > 0. n == 0 returns 0 and writes nothing; F == 0 zeroes the
+ * outputs without a launch. */
+int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, const int32_t* feat_col,
+                             const int32_t* feat_start, const int32_t* feat_end, int64_t F, int64_t* removed_bp,
+                             int32_t* genes_removed, uint64_t* signature, void* stream);
+
 /* calculate_reconstruction_metrics (training/evaluation/metrics.py:19-64) without materialising the
  * reconstruction: eval-mode model(x) of `batch` (eps given: the reference samples z there too), then
  * per strain counts[i] = (TP, FP, FN) of (recon > threshold) against the strain's genes. */

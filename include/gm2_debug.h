@@ -19,7 +19,8 @@ extern "C" {
 #define GM2_DBG_RESIDENT_ROWS 1  /* a batch row index outside the resident matrix [0, S) */
 #define GM2_DBG_GATHER_ROWS 2    /* a negative gather row index */
 #define GM2_DBG_GEMM_IDX 4       /* a zero-copy GEMM row-table entry outside the resident operands */
-#define GM2_DBG_MASK_POS 8       /* gm2_mask_count_groups: descending group offsets / position past the row */
+#define GM2_DBG_MASK_POS 8       /* gm2_mask_count_groups: descending group offsets / position past the row;
+                                    gm2_mask_minimized_stats: a feature column outside [-2, G) */
 #define GM2_DBG_COMPACT 16       /* gm2_mask_compact: an index written outside its row's CSR span */
 #define GM2_DBG_RECON_ROWS 32    /* loss epilogue: a target-bit row outside the resident bits */
 #define GM2_DBG_TILE 64          /* a GEMM tile or K range outside the padded operand extents */

@@ -41,6 +41,10 @@ with --nearest-strains, for the samples by their nearest strain's phylogroup. --
 mode, off by default) compares which genes travel together: the gene x gene co-occurrence counts of a
 panel of --linkage-genes intermediate-frequency genes in the strains and in the samples, from the
 gene-major packed rows (gm2_mask_transpose, then gm2_mask_cooccur; gm2/linkage.py), as phi coefficients.
+--minimized-sizes (sample mode, off by default; --genome-path, --minimized-fill essentials|none) reports
+what convert-samples + --mode minimizer would make of every sampled genome -- genes removed, reduced
+length, duplicate group -- from the packed rows and the GenBank record's gene features
+(gm2_mask_minimized_stats; gm2/minsizes.py), without gene lists or FASTA.
 """
 import argparse
 import os
@@ -85,6 +89,12 @@ def parse_arguments(argv=None):
                    help="sample mode: gene-gene linkage (phi) of the sampled genomes against the dataset strains (CSV)")
     p.add_argument("--linkage-genes", type=int, default=2048,
                    help="sample mode, --gene-linkage: the most genes of the linkage panel")
+    p.add_argument("--minimized-sizes", action="store_true",
+                   help="sample mode: minimized genome size and duplicate group of every sampled genome (CSV), "
+                        "computed on the packed masks without writing sequences")
+    p.add_argument("--minimized-fill", choices=["essentials", "none"], default="essentials",
+                   help="sample mode, --minimized-sizes: keep every essential gene as convert-samples' "
+                        "_with_essentials lists do (essentials) or only the sampled genes (none)")
     p.add_argument("--genome-path", type=str, default=None,
                    help="GenBank genome (default: <project root>/data/wild_type_sequence.gb)")
     p.add_argument("--output-dir", type=str, default="./minimized_genomes")
@@ -277,6 +287,43 @@ def compare_with_strains(args, packed, sizes, merged, out_dir, tag):
         plt.close(fig)
 
 
+def minimized_sizes(args, packed, sizes, path):
+    """--minimized-sizes: what --mode convert-samples + --mode minimizer would report for these samples
+    (reduced length, genes removed, duplicate groups), from the packed rows on the device
+    (PackedMasks.minimized_stats, gm2/minsizes.py); no gene list and no FASTA is written."""
+    import numpy as np
+    import pandas as pd
+    from gm2 import minsizes
+    from gm2.minimizer import read_genbank
+    genome_path = args.genome_path or os.path.join(args.project_root, "data", "wild_type_sequence.gb")
+    if not os.path.exists(genome_path):
+        print(f"✗ Genome file not found: {genome_path}")
+        return False
+    paths = data_paths(args.project_root)
+    # the gene column names as run_binary_converter takes them
+    large = pd.read_csv(paths["Main Dataset"], index_col=0)
+    cols = large.drop(index=["Lineage"], errors="ignore").transpose().columns
+    if len(cols) != packed.G:
+        print(f"✗ The dataset has {len(cols)} gene columns, the sampled masks {packed.G}")
+        return False
+    essential_set = None
+    if args.minimized_fill == "essentials":
+        ess = pd.read_csv(paths["Essential Genes"])   # binary_converter.load_files
+        essential_set = set(ess["# gene" if "# gene" in ess.columns else "gene"].astype(str).str.strip())
+    plan = minsizes.FeaturePlan.build(read_genbank(genome_path), cols, essential_set)
+    stats = packed.minimized_stats(plan)
+    table = minsizes.size_table(stats, sizes, plan.L)
+    table.to_csv(path, index=False)
+    red, dup = stats["reduced_length"], minsizes.duplicate_stats(stats["signature"])
+    print(f"- Minimized genomes ({Path(genome_path).name}, {plan.L:,} bp, {plan.F} gene features, "
+          f"fill: {args.minimized_fill}): median reduced length {np.median(red):.0f} bp, "
+          f"range {red.min()} - {red.max()}")
+    print(f"- Mean reduction: {table['reduction_pct'].mean():.2f}%")
+    print(f"- Unique minimized genomes: {dup['unique_sequences']} of {dup['total_sequences']}; "
+          f"duplicate groups: {dup['duplicate_groups']}\n- Minimized sizes: {path}")
+    return True
+
+
 def run_sampling(args):
     """main.py:219-446 without the reference's plots: load the checkpoint, decode in fp32, threshold,
     count essential genes, save masks (.npy) and the genes x samples CSV; --nearest-strains / --pca
@@ -352,6 +399,9 @@ def run_sampling(args):
     print(f"- Essential range: {np.min(ess):.0f} - {np.max(ess):.0f}")
     if args.nearest_strains or args.pca or args.gene_frequencies or args.gene_linkage:
         compare_with_strains(args, packed, sizes, merged, out_dir, config.trainer_version)
+    if args.minimized_sizes and packed.n and not minimized_sizes(
+            args, packed, sizes, out_dir / f"{config.trainer_version}_minimized_sizes_{args.sampling_mode}.csv"):
+        return False
     if args.mask_dtype == "bits":
         out = packed.to_host()
     else:

@@ -246,6 +246,35 @@ static void error_paths() {
   expect_error(gm2_mask_transpose(tr_in, 4, 16, 100, nullptr, 16, nullptr), "null", "transpose null out");
   expect_error(gm2_mask_transpose(tr_out, 4, 16, 100, tr_out + 48, 16, nullptr), "overlap", "transpose out inside bits");
   CHECK(gm2_mask_transpose(tr_in, 0, 16, 100, tr_out, 16, nullptr) == 0, "transpose of no rows");
+  // minimized sizes: 2 rows of 100 genes, 3 features; every refusal is host-side
+  int32_t ft[3] = {0, -1, -2};
+  int64_t ms_bp[2];
+  int32_t ms_gone[2];
+  uint64_t ms_sig[2];
+  expect_error(gm2_mask_minimized_stats(rows_a, -1, 16, 100, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "negative",
+               "minimized_stats n < 0");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 0, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "G",
+               "minimized_stats G = 0");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 100, ft, ft, ft, -1, ms_bp, ms_gone, ms_sig, nullptr), "F",
+               "minimized_stats F < 0");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 24, 100, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "pitch",
+               "minimized_stats pitch % 16");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 129, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "pitch",
+               "minimized_stats pitch < G bits");
+  expect_error(gm2_mask_minimized_stats(rows_a + 8, 2, 16, 100, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "aligned",
+               "minimized_stats misaligned bits");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 100, (int32_t*)((char*)ft + 2), ft, ft, 3, ms_bp, ms_gone, ms_sig,
+                                        nullptr), "aligned", "minimized_stats misaligned table");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 100, ft, ft, ft, 3, (int64_t*)((char*)ms_bp + 4), ms_gone, ms_sig,
+                                        nullptr), "aligned", "minimized_stats misaligned removed_bp");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 100, ft, nullptr, ft, 3, ms_bp, ms_gone, ms_sig, nullptr), "null",
+               "minimized_stats null table");
+  expect_error(gm2_mask_minimized_stats(rows_a, 2, 16, 100, ft, ft, ft, 3, ms_bp, nullptr, ms_sig, nullptr), "null",
+               "minimized_stats null output");
+  CHECK(gm2_mask_minimized_stats(rows_a, 0, 16, 100, ft, ft, ft, 3, ms_bp, ms_gone, ms_sig, nullptr) == 0,
+        "minimized_stats of no rows");
+  CHECK(gm2_mask_minimized_stats(rows_a, 0, 16, 100, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == 0,
+        "minimized_stats of no rows and no features");
   std::string last = gm2_last_error();
   CHECK(!last.empty(), "an error message is kept");
   unsigned flags = 1;
