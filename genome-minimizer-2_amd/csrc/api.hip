@@ -108,6 +108,11 @@ struct Layout {
   // GEMM shadows (T), natural [out][in] layout, zero-padded: each serves as a K-major operand in
   // the forward GEMM and as an MN-major operand ([K=out][N=in]) in the backward dX GEMM
   int64_t sE0, sE1, sE2, sHD, sD0, sD1, sD2, sD3;
+  // the Linear weight of BatchNorm block i (kBlk)
+  int64_t shadow(int i) const {
+    const int64_t s[6] = {sE0, sE1, sE2, sD0, sD1, sD2};
+    return s[i];
+  }
   int64_t X, XB, Y[6], A[6], save[6], HD, Z, dL, slabs, slab_cap, side_slabs, side_cap, dY[6], DA, dH;
   int64_t AT5, dYT0;  // transposed A5 / dY0 [H][Bm]: K-major operands of the dW9 / dWe0 GEMMs
   int64_t bnpart, colpart, colpart_cap, losspart, losspart_cap, klpart, gradpart, clip, scal0, total;
@@ -255,6 +260,14 @@ Layout make_layout(const gm2_dims* gd, int prec) {
 
 struct WsState;
 
+// the one f32 / bf16 branch: f(T{}) with T the element type of a GM2_F32 / GM2_BF16 layout
+// (Layout::prec; a GM2_BF16X3 workspace has the GM2_F32 layout)
+template <typename F>
+void by_precision(int prec, F&& f) {
+  if (prec == GM2_F32) f(float{});
+  else f(bf16_t{});
+}
+
 template <typename T>
 struct Ctx {
   const Layout& lo;
@@ -278,18 +291,10 @@ struct Ctx {
       : lo(l), ws((char*)w), s((hipStream_t)strm), d(l.d), slab_off(l.slabs), slab_cap(l.slab_cap), xo(l.X),
         xbo(l.XB), st(state) {}
   Ctx side(hipStream_t strm) const {
-    Ctx c(lo, ws, strm, st);
+    Ctx c(*this);
+    c.s = strm;
     c.slab_off = lo.side_slabs;
     c.slab_cap = lo.side_cap;
-    c.xo = xo;
-    c.xbo = xbo;
-    c.ridx = ridx;
-    c.xres = xres;
-    c.ld_xres = ld_xres;
-    c.xbres = xbres;
-    c.ld_xbres = ld_xbres;
-    c.res_rows = res_rows;
-    c.x3 = x3;
     return c;
   }
   T* t(int64_t off) const { return (T*)(ws + off); }
@@ -402,8 +407,9 @@ struct WsState {
   }
   void launch_queued(hipStream_t s, int max_grid = 0) {
     QueuedAdam& q = qadam;
-    if (q.prec == GM2_F32) launch_adam_fused<float>(q.tt, q.g, q.p, q.m, q.v, q.scal, q.clip, s, max_grid);
-    else launch_adam_fused<bf16_t>(q.tt, q.g, q.p, q.m, q.v, q.scal, q.clip, s, max_grid);
+    by_precision(q.prec, [&](auto tag) {
+      launch_adam_fused<decltype(tag)>(q.tt, q.g, q.p, q.m, q.v, q.scal, q.clip, s, max_grid);
+    });
     q.queued = false;
   }
   // a training call's forward, after its input-layer GEMM: start the queued output-layer update on
@@ -565,10 +571,8 @@ BigGrads<T> big_grads(const Ctx<T>& c, int Bp) {
   BigGrads<T> r{{c.t(l.AT5), Bp, c.t(l.dL), Gp, H, G, Bp, H, Gp, 0, 1, 0},
                 {c.t(l.dYT0), Bp, c.t(c.xo), Gp, H, G, Bp, H, Gp, 0, 1, 0}, false, 0, 0};
   if (c.ridx) {  // zero-copy rows: X's rows are the resident matrix's, through ridx
-    r.g0.Q = c.xres;
-    r.g0.ldq = c.ld_xres;
-    r.g0.qrow = c.ridx;
-    r.g0.idx_lim = c.res_rows;
+    r.g0.Q = c.xres, r.g0.ldq = c.ld_xres;
+    r.g0.qrow = c.ridx, r.g0.idx_lim = c.res_rows;
   }
   r.direct = plan_gemm<T>(r.g9).splits == 1 && plan_gemm<T>(r.g0).splits == 1;
   r.n9 = gemm_tiles<T>(r.g9);
@@ -581,24 +585,6 @@ BigGrads<T> big_grads(const Ctx<T>& c, int Bp) {
 // the 6 BatchNorm blocks: (linear weight, linear bias, bn gamma, bn beta)
 const int kBlk[6][4] = {{E0W, E0B, E1G, E1BT}, {E3W, E3B, E4G, E4BT}, {E6W, E6B, E7G, E7BT},
                         {D0W, D0B, D1G, D1BT}, {D3W, D3B, D4G, D4BT}, {D6W, D6B, D7G, D7BT}};
-
-// Pre-BatchNorm Linear: Y = in . W^T + bias (fp32 [Bp][H]) and, when `stats`, the per-128-row
-// chunk (mean, M2) partials of Y -> part. One launch when the GEMM plan is a single pass of 128-row
-// tiles (statistics in the store epilogue); otherwise split-K slabs + k_bn_fwd_partial.
-template <typename T>
-void linear_pre_bn(const Ctx<T>& c, const T* in, int64_t ldin, int Bp, const T* W, int64_t ldw, int B, int H, int K,
-                   const float* bias, float* Y, float* part, bool stats, const int32_t* prow = nullptr) {
-  GemmArgs<T> g{in, ldin, W, ldw, B, H, K, Bp, H, 0};
-  StoreEpi bn;
-  bn.mode = stats ? 1 : 0;
-  bn.part = (float2*)part;
-  bn.ldp = H;
-  if (!prow && launch_gemm_bn<T>(g, Y, H, bias, bn, c.s)) return;
-  g.prow = prow;
-  if (prow) g.idx_lim = c.res_rows;
-  const int S = gemm_to_slabs(c, g, H);
-  launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)Bp * H, H, bias, B, H, Y, part, c.s);
-}
 
 // ---------------------------------------------------------------------------------------------
 // GM2_BF16X3: which of the five G-wide GEMMs of a call run as split-bf16 products, with their
@@ -659,14 +645,8 @@ TensorTable make_table(const Ctx<T>& c, int kind = 0) {
   };
   auto add = [&](int pi, int64_t rows, int64_t cols, int64_t sh, int64_t sld, int64_t srow0) {
     TensorDesc& e = tt.t[tt.n];
-    e.off = d.off[pi];
-    e.rows = rows;
-    e.cols = cols;
-    e.shadow = sh >= 0 ? (void*)(c.ws + sh) : nullptr;
-    e.sld = sld;
-    e.srow0 = srow0;
-    e.shadowT = nullptr;
-    e.tld = 0;
+    e.off = d.off[pi], e.rows = rows, e.cols = cols, e.shadowT = nullptr, e.tld = 0;
+    e.shadow = sh >= 0 ? (void*)(c.ws + sh) : nullptr, e.sld = sld, e.srow0 = srow0;
     e.tile0 = tt.n == 0 ? 0 : tt.t[tt.n - 1].tile0 + tiles_of(tt.t[tt.n - 1]);
     tt.n++;
   };
@@ -716,105 +696,179 @@ TensorTable table_range(const TensorTable& tt, int lo, int hi) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// forward (train or eval). Fills A_l (+A_l^T when train), Y_l, save_l, HD, Z, ZT and runs the
-// fused reconstruction-loss epilogue (dL, dL^T when with_grad).
+// The forward schedule, written once: one Linear -> BatchNorm -> ReLU layer (bn_layer), the encoder
+// half (rows, layers 0-2, heads + reparameterisation) and the decoder half (layers 3-5).
 // ---------------------------------------------------------------------------------------------
+// what the six BatchNorm layers of one pass share: parameters, running statistics [6][2H], rows
+struct BnPass {
+  const float* prm;
+  float* bn;
+  int B, Bp;
+  int train = 0;      // batch statistics (Linear epilogue partials, running-statistics update)
+  bool sync = false;  // SyncBN: the batch statistics span every rank's rows
+  bool save = false;  // keep each layer's batch mean / invstd (Layout::save), as a backward needs
+};
+
+// Pre-BatchNorm Linear of layer i: Y_i = in . W_i^T + bias (fp32 [Bp][H]) and, when training, the
+// per-128-row chunk (mean, M2) partials of Y_i -> bnpart. One launch when the GEMM plan is a single
+// pass of 128-row tiles (statistics in the store epilogue); otherwise split-K slabs +
+// k_bn_fwd_partial. prow: the rows of `in` through a row table (zero-copy rows).
 template <typename T>
-void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, int train, int with_grad,
-             const float* scal, double* loss, float* grads, float* probs = nullptr, int64_t ld_probs = 0,
-             int* counts = nullptr, float thr = 0.5f, bool norm_hdr = false, bool staged = false,
-             std::function<void(hipStream_t)>* defer_tail = nullptr) {
+void linear_pre_bn(const Ctx<T>& c, const BnPass& p, int i, const T* in, int64_t ldin, int K, int64_t ldw,
+                   const int32_t* prow = nullptr) {
+  const Layout& l = c.lo;
+  const int H = (int)c.d.H;
+  const float* bias = p.prm + c.d.off[kBlk[i][1]];
+  GemmArgs<T> g{in, ldin, c.t(l.shadow(i)), ldw, p.B, H, K, p.Bp, H, 0};
+  StoreEpi bn;
+  bn.mode = p.train ? 1 : 0, bn.part = (float2*)c.f(l.bnpart), bn.ldp = H;
+  if (!prow && launch_gemm_bn<T>(g, c.f(l.Y[i]), H, bias, bn, c.s)) return;
+  g.prow = prow;
+  if (prow) g.idx_lim = c.res_rows;
+  const int S = gemm_to_slabs(c, g, H);
+  launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)p.Bp * H, H, bias, p.B, H, c.f(l.Y[i]), c.f(l.bnpart), c.s);
+}
+
+// BatchNorm + ReLU of layer i: Y_i and its partials -> A_i
+template <typename T>
+void bn_apply(const Ctx<T>& c, const BnPass& p, int i) {
+  const Layout& l = c.lo;
+  const int H = (int)c.d.H;
+  double* syncb = (double*)(c.ws + l.syncb);
+  if (p.sync) {  // SyncBN: this rank's column sums -> all-reduce -> the global batch's statistics
+    launch_bn_sync_pack(c.f(l.bnpart), p.B, H, 0, syncb, c.s);
+    c.st->allreduce(syncb, 2 * H + 2, c.s);
+  }
+  float* run = p.bn + (int64_t)i * 2 * H;
+  launch_bn_fwd_apply<T>(c.f(l.Y[i]), H, c.f(l.bnpart), p.B, p.Bp, H, p.train, p.prm + c.d.off[kBlk[i][2]],
+                         p.prm + c.d.off[kBlk[i][3]], run, run + H, p.save ? c.f(l.save[i]) : nullptr, c.t(l.A[i]),
+                         c.s, p.sync ? syncb : nullptr);
+}
+
+template <typename T>
+void bn_layer(const Ctx<T>& c, const BnPass& p, int i, const T* in, int64_t ldin, int K, int64_t ldw) {
+  linear_pre_bn<T>(c, p, i, in, ldin, K, ldw);
+  bn_apply<T>(c, p, i);
+}
+
+// Encoder half. The batch's rows: in place through c.ridx, already `staged` by the previous training
+// call, or gathered into the input slot (with their bit-packed target when `target_bits`). Then
+// layers 0-2 and the heads GEMM + reparameterisation with b->eps: HD = mu | logvar, Z.
+template <typename T>
+void encoder_half(const Ctx<T>& c, const gm2_batch* b, const BnPass& p, const X3Plan& xp, bool target_bits,
+                  bool staged = false, bool with_grad = false) {
   const Dims& d = c.d;
   const Layout& l = c.lo;
-  const int B = (int)b->n;
-  if (B <= 0 || B > d.Bm) throw Gm2Error("batch rows %d outside (0, batch_max=%lld]", B, (long long)d.Bm);
-  const bool sync = train && c.st && c.st->opt.sync_bn;
-  // (SyncBN: the batch statistics span every rank's rows, so one row here is fine)
-  if (train && B < 2 && !sync) throw Gm2Error("Expected more than 1 value per channel when training (batch of 1)");
-  check_batch_data(b, d, "batch");
-  double* syncb = (double*)(c.ws + l.syncb);
-  const int Bp = (int)round_up(B, kTile);
-  const int H = (int)d.H, L = (int)d.L;
-  // 1) strain rows -> X [Bp][Gp] (T) + bit-packed target (unless a previous training call staged
-  // them, or the call reads the resident matrix's rows in place: c.ridx)
+  const int B = p.B, Bp = p.Bp, H = (int)d.H, L = (int)d.L;
+  const int64_t Gq = l.Gq;
   if (c.ridx)
     launch_resident_rows(b->rows, B, (int)round_up(d.Bm, 2 * kTile), b->resident_rows, const_cast<int32_t*>(c.ridx),
                          c.s);
   else if (!staged)
     launch_gather_rows<T>(b->data, b->ld_data, b->rows, B, (int)d.G, c.t(c.xo), d.Gp, (int)d.Gp, Bp,
-                          (uint32_t*)(c.ws + c.xbo), d.Gp / 32, c.s);
-  // 2) encoder blocks, heads + reparameterisation, decoder blocks (all NT GEMMs)
-  const T* in = c.ridx ? c.xres : c.t(c.xo);
-  int64_t ldin = c.ridx ? c.ld_xres : d.Gp;
-  int Kin = (int)d.Gp;
-  const int64_t shadow_in[6] = {l.sE0, l.sE1, l.sE2, l.sD0, l.sD1, l.sD2};
+                          target_bits ? (uint32_t*)(c.ws + c.xbo) : nullptr, target_bits ? d.Gp / 32 : 0, c.s);
+  // bf16x3: X as (x | x) for a split input layer, and once more plain for a split dWe0 in the
+  // backward (also beside the exact input layer: X in bf16 all the same)
+  const bool keep_x = with_grad && xp.dwe0;
+  if (xp.enc0 || keep_x)
+    launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1,
+                        keep_x ? c.h(l.x3x) : nullptr, Gq, c.s);
+  if (xp.enc0) {
+    // the fp32 weight shadow split per call (an Adam step or a shadow sync in between is always seen)
+    launch_split_kmajor(c.f(l.sE0), d.Gp, H, (int)d.G, H, (int)Gq, c.h(l.x3w0), 2 * Gq, 0, nullptr, 0, c.s);
+    const int S = gemm_to_slabs(c, xp.g_enc0, H);
+    launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)xp.Bq * H, H, p.prm + d.off[E0B], B, H, c.f(l.Y[0]),
+                          c.f(l.bnpart), c.s);
+  } else {
+    linear_pre_bn<T>(c, p, 0, c.ridx ? c.xres : c.t(c.xo), c.ridx ? c.ld_xres : d.Gp, (int)d.Gp, d.Gp, c.ridx);
+  }
+  // a queued output-layer Adam update of the previous step starts here, beside the hidden layers
+  // (HBM-bound next to latency-bound small GEMMs; the gather and the input-layer GEMM before this
+  // point leave it nothing: one is HBM-bound too, the other holds every CU's registers)
+  if (c.st) c.st->kick(c.s);
+  bn_apply<T>(c, p, 0);
+  bn_layer<T>(c, p, 1, c.t(l.A[0]), H, H, H);
+  bn_layer<T>(c, p, 2, c.t(l.A[1]), H, H, H);
+  const int S = gemm_to_slabs(c, GemmArgs<T>{c.t(l.A[2]), H, c.t(l.sHD), H, B, 2 * L, H, Bp, (int)d.L2r, 0}, 2 * L);
+  launch_reparam<T>(c.f(l.slabs), S, (int64_t)Bp * 2 * L, L, p.prm + d.off[MUB], p.prm + d.off[LVB], b->eps, B, Bp,
+                    c.f(l.HD), c.t(l.Z), d.Lr, nullptr, 0, 0, c.f(l.klpart), c.s);
+}
+
+// Decoder half: Z [Bp][Lr] through layers 3-5 -> A5
+template <typename T>
+void decoder_half(const Ctx<T>& c, const BnPass& p) {
+  const Layout& l = c.lo;
+  const int H = (int)c.d.H;
+  bn_layer<T>(c, p, 3, c.t(l.Z), c.d.Lr, (int)c.d.Lp, c.d.Lr);
+  bn_layer<T>(c, p, 4, c.t(l.A[3]), H, H, H);
+  bn_layer<T>(c, p, 5, c.t(l.A[4]), H, H, H);
+}
+
+// mu / logvar [B][L] of the last encoder half (HD = mu | logvar) -> the caller's buffers
+template <typename T>
+void copy_heads(const Ctx<T>& c, int64_t B, float* mu, float* logvar) {
+  const int64_t L = c.d.L;
+  const float* hd = c.f(c.lo.HD);
+  if (mu) HIP_OK(hipMemcpy2DAsync(mu, L * 4, hd, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
+  if (logvar) HIP_OK(hipMemcpy2DAsync(logvar, L * 4, hd + L, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
+}
+
+// What one forward() call is for: the fused loss (scal, loss; with_grad: dL and grads too), or
+// VAE.forward's probs [B][ld_probs] / per-strain (TP, FP, FN) counts of (p > thr), without a loss
+struct FwdCall {
+  int train = 0, with_grad = 0;
+  const float* scal = nullptr;  // scalar block of the loss terms
+  double* loss = nullptr;
+  float *grads = nullptr, *probs = nullptr;
+  int64_t ld_probs = 0;
+  int* counts = nullptr;
+  float thr = 0.5f;
+  bool norm_hdr = false;  // record whether the backward takes the clip statistics (NormAhead)
+  bool staged = false;    // the rows are in the input slot already (SlotState)
+  std::function<void(hipStream_t)>* defer_tail = nullptr;  // receives the tail launch instead of running it
+};
+
+// forward (train or eval). Fills A_l, Y_l, save_l, HD, Z and runs the fused reconstruction-loss
+// epilogue (dL when with_grad), or the probabilities / counts epilogue.
+template <typename T>
+void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, const FwdCall& f) {
+  const Dims& d = c.d;
+  const Layout& l = c.lo;
+  const int B = (int)b->n;
+  if (B <= 0 || B > d.Bm) throw Gm2Error("batch rows %d outside (0, batch_max=%lld]", B, (long long)d.Bm);
+  const bool sync = f.train && c.st && c.st->opt.sync_bn;
+  // (SyncBN: the batch statistics span every rank's rows, so one row here is fine)
+  if (f.train && B < 2 && !sync) throw Gm2Error("Expected more than 1 value per channel when training (batch of 1)");
+  check_batch_data(b, d, "batch");
+  const int Bp = (int)round_up(B, kTile), H = (int)d.H;
+  // 1, 2) strain rows, encoder blocks, heads + reparameterisation, decoder blocks (all NT GEMMs)
   const X3Plan xp = x3_plan<T>(c, B);
   const int64_t Gq = l.Gq;
-  for (int i = 0; i < 6; ++i) {
-    if (i == 3) {
-      const int S = gemm_to_slabs(c, GemmArgs<T>{c.t(l.A[2]), H, c.t(l.sHD), H, B, 2 * L, H, Bp, (int)d.L2r, 0}, 2 * L);
-      launch_reparam<T>(c.f(l.slabs), S, (int64_t)Bp * 2 * L, L, prm + d.off[MUB], prm + d.off[LVB], b->eps, B, Bp,
-                        c.f(l.HD), c.t(l.Z), d.Lr, nullptr, 0, 0, c.f(l.klpart), c.s);
-      in = c.t(l.Z);
-      ldin = d.Lr;
-      Kin = (int)d.Lp;
-    }
-    if (i == 0 && xp.enc0) {
-      // bf16x3 input layer: X as (x | x) (and once more plain, for the backward's dWe0), the fp32
-      // weight shadow split per call (an Adam step or a shadow sync in between is always seen)
-      launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1,
-                          with_grad && xp.dwe0 ? c.h(l.x3x) : nullptr, Gq, c.s);
-      launch_split_kmajor(c.f(l.sE0), d.Gp, H, (int)d.G, H, (int)Gq, c.h(l.x3w0), 2 * Gq, 0, nullptr, 0, c.s);
-      const int S = gemm_to_slabs(c, xp.g_enc0, H);
-      launch_bn_fwd_partial(c.f(c.slab_off), S, (int64_t)xp.Bq * H, H, prm + d.off[kBlk[i][1]], B, H, c.f(l.Y[i]),
-                            c.f(l.bnpart), c.s);
-    } else {
-      if (i == 0 && with_grad && xp.dwe0)  // (the exact input layer beside a split dWe0: X in bf16 all the same)
-        launch_split_kmajor(c.f(c.xo), d.Gp, B, (int)d.G, xp.Bq, (int)Gq, c.h(l.x3xd), 2 * Gq, 1, c.h(l.x3x), Gq, c.s);
-      linear_pre_bn<T>(c, in, ldin, Bp, c.t(shadow_in[i]), i == 3 ? d.Lr : Kin, B, H, Kin, prm + d.off[kBlk[i][1]],
-                       c.f(l.Y[i]), c.f(l.bnpart), train != 0, i == 0 ? c.ridx : nullptr);
-    }
-    // a queued output-layer Adam update of the previous step starts here, beside the hidden layers
-    // (HBM-bound next to latency-bound small GEMMs; the gather and the input-layer GEMM before this
-    // point leave it nothing: one is HBM-bound too, the other holds every CU's registers)
-    if (i == 0 && c.st) c.st->kick(c.s);
-    if (sync) {  // SyncBN: this rank's column sums -> all-reduce -> the global batch's statistics
-      launch_bn_sync_pack(c.f(l.bnpart), B, H, 0, syncb, c.s);
-      c.st->allreduce(syncb, 2 * H + 2, c.s);
-    }
-    launch_bn_fwd_apply<T>(c.f(l.Y[i]), H, c.f(l.bnpart), B, Bp, H, train, prm + d.off[kBlk[i][2]],
-                           prm + d.off[kBlk[i][3]], bn + (int64_t)i * 2 * H, bn + (int64_t)i * 2 * H + H,
-                           c.f(l.save[i]), c.t(l.A[i]), c.s, sync ? syncb : nullptr);
-    in = c.t(l.A[i]);
-    ldin = H;
-    Kin = H;
-  }
+  const BnPass p{prm, bn, B, Bp, f.train, sync, /*save=*/true};
+  encoder_half<T>(c, b, p, xp, true, f.staged, f.with_grad != 0);
+  decoder_half<T>(c, p);
   if (c.st) c.st->join(c.s);  // (a deferred output-layer update must be complete before the output layer)
-  if (probs || counts) {  // 3') VAE.forward: p = sigmoid(logits) (model.py:89-90) and / or the
-                          // per-strain (TP, FP, FN) of (p > thr) vs the strain's genes; no loss
+  if (f.probs || f.counts) {  // 3') VAE.forward: p = sigmoid(logits) (model.py:89-90) and / or the
+                              // per-strain (TP, FP, FN) of (p > thr) vs the strain's genes; no loss
     GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, B, (int)d.G, H, Bp, (int)d.Gp, 0};
-    launch_gemm_mask<T>(g, prm + d.off[D9B], nullptr, 0, probs, ld_probs, c.s, nullptr, 0, counts,
-                        (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, thr);
+    launch_gemm_mask<T>(g, prm + d.off[D9B], nullptr, 0, f.probs, f.ld_probs, c.s, nullptr, 0, f.counts,
+                        (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, f.thr);
     return;
   }
-  // 3) output layer + reconstruction loss (+ dlogits), computed as logit^T: genes x strains. A
-  // deferred output-layer Adam update of the previous step (side stream) must be complete here.
-  if (c.st) c.st->join(c.s);
+  // 3) output layer + reconstruction loss (+ dlogits), computed as logit^T: genes x strains
   GemmArgs<T> g{c.t(l.sD3), H, c.t(l.A[5]), H, (int)d.G, B, H, (int)d.Gp, Bp, 0};
   if (c.ridx) g.idx_lim = c.res_rows;
   if (xp.loss) {
     launch_split_kmajor(c.f(l.sD3), H, (int)d.G, H, (int)Gq, H, c.h(l.x3w9k), 2 * H, 0, nullptr, 0, c.s);
     launch_split_kmajor(c.f(l.A[5]), H, B, H, xp.Bq, H, c.h(l.x3a5k), 2 * H, 0, nullptr, 0, c.s);
-    launch_gemm_recon_loss_x3(xp.g_loss, prm + d.off[D9B], (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, with_grad, scal,
-                              c.f(l.dL), d.Gp, (int)d.Gp, Bp, c.f(l.losspart), c.f(l.colpart), d.Gp, c.s);
-  } else if (c.ridx)
-    launch_gemm_recon_loss<T>(g, prm + d.off[D9B], c.xbres, c.ld_xbres, with_grad, scal, c.t(l.dL), d.Gp,
+    launch_gemm_recon_loss_x3(xp.g_loss, prm + d.off[D9B], (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, f.with_grad,
+                              f.scal, c.f(l.dL), d.Gp, (int)d.Gp, Bp, c.f(l.losspart), c.f(l.colpart), d.Gp, c.s);
+  } else  // (zero-copy rows: the resident matrix's target bits through the row table)
+    launch_gemm_recon_loss<T>(g, prm + d.off[D9B], c.ridx ? c.xbres : (const uint32_t*)(c.ws + c.xbo),
+                              c.ridx ? c.ld_xbres : d.Gp / 32, f.with_grad, f.scal, c.t(l.dL), d.Gp,
                               c.f(l.losspart), c.f(l.colpart), d.Gp, c.s, c.ridx);
-  else
-    launch_gemm_recon_loss<T>(g, prm + d.off[D9B], (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, with_grad, scal,
-                              c.t(l.dL), d.Gp, c.f(l.losspart), c.f(l.colpart), d.Gp, c.s);
   int na_ok = 0, na_n = 0;
-  if (norm_hdr) {  // the training call: record whether its backward takes the clip statistics
+  if (f.norm_hdr) {  // the training call: record whether its backward takes the clip statistics
     const BigGrads<T> bg = big_grads<T>(c, Bp);
     na_ok = bg.direct && !xp.dw9 && !xp.dwe0 ? 1 : 0;  // (the split weight gradients take no clip statistics)
     na_n = bg.n9 + bg.n0;
@@ -823,19 +877,19 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, i
   // reads them before its final join, so a training call hands the launch to the backward, which
   // puts it on the side stream behind its first fork (off the critical path, one launch and its
   // gap fewer on the caller's stream)
-  const float* lpart = c.f(l.losspart);
   const int nlp = xp.loss ? (int)(Gq / 256) * (xp.Bq / 256) : gemm_recon_grid_blocks<T>(g);
   const int nkp = Bp / kReparamRows, rt = xp.loss ? xp.Bq / 256 : gemm_recon_row_tiles<T>(g);
-  const float *kpart = c.f(l.klpart), *cpart = c.f(l.colpart);
+  const float *lpart = c.f(l.losspart), *kpart = c.f(l.klpart), *cpart = c.f(l.colpart);
   const int64_t Gp = d.Gp, G = d.G;
-  float* bgrad = with_grad ? grads + d.off[D9B] : nullptr;
-  int* hdr = norm_hdr ? (int*)(c.ws + l.nahdr) : nullptr;
+  double* loss = f.loss;
+  float* bgrad = f.with_grad ? f.grads + d.off[D9B] : nullptr;
+  int* hdr = f.norm_hdr ? (int*)(c.ws + l.nahdr) : nullptr;
   auto tail = [=](hipStream_t s) {
     launch_fwd_tail(lpart, nlp, kpart, nkp, loss, cpart, rt, Gp, G, bgrad, hdr, na_ok, na_n, s);
   };
   // (env GM2_TAIL_MAIN: on the caller's stream, as before; A/B profiles/r03_fwd_tail_side_ab.txt)
   static const bool tail_main = std::getenv("GM2_TAIL_MAIN") != nullptr;
-  if (defer_tail && !tail_main) *defer_tail = tail;
+  if (f.defer_tail && !tail_main) *f.defer_tail = tail;
   else tail(c.s);
 }
 
@@ -846,13 +900,21 @@ struct NextStage {
   hipEvent_t done = nullptr;
 };
 
+// What one backward() call adds to the plain backward of the fused loss
+struct BwdCall {
+  const float *dmu_ext = nullptr, *dlv_ext = nullptr;  // d(mu), d(logvar) from outside the fused loss
+  int train = 1;
+  const NextStage* next = nullptr;
+  std::function<void(hipStream_t)>* fwd_tail = nullptr;  // the forward's deferred tail launch
+};
+
 // Backward. Every operand is read in the layout its producer wrote: weight gradients use MN-major P
 // and Q (dW[out][in] = sum_b dY[b][out] * in[b][in]), input gradients an MN-major weight
 // (dX[b][in] = sum_out dY[b][out] * W[out][in]); no transposed copy exists anywhere.
 template <typename T>
 void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, const float* scal,
-              const float* dmu_ext = nullptr, const float* dlv_ext = nullptr, int train = 1,
-              const NextStage* nx = nullptr, std::function<void(hipStream_t)>* fwd_tail = nullptr) {
+              const BwdCall& bw) {
+  const NextStage* nx = bw.next;
   const Dims& d = c.d;
   const Layout& l = c.lo;
   const int B = (int)b->n, Bp = (int)round_up(B, kTile);
@@ -876,17 +938,16 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     const char* e = std::getenv("GM2_FORK_HOLD");
     return e ? std::max(1, std::atoi(e)) : 3;
   }();
-  const bool fork_batch = true;
   std::vector<std::function<void()>> held;
   auto side_work = [&](bool hold, std::function<void()> f) {
-    if (hold && sr && fork_batch) {
+    if (hold && sr) {
       held.push_back(std::move(f));
       return;
     }
     f();
   };
   auto fork_flush = [&](bool hold) {
-    if (hold && sr && fork_batch) return;
+    if (hold && sr) return;
     fork();
     for (auto& f : held) f();
     held.clear();
@@ -904,9 +965,9 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
   double* nasq = (double*)(c.ws + l.nasq);
   // the forward's deferred tail launch (loss sums, output bias gradient): behind the first fork
   auto tail_on = [&](hipStream_t s) {
-    if (fwd_tail && *fwd_tail) {
-      (*fwd_tail)(s);
-      *fwd_tail = nullptr;
+    if (bw.fwd_tail && *bw.fwd_tail) {
+      (*bw.fwd_tail)(s);
+      *bw.fwd_tail = nullptr;
     }
   };
   // The output-layer weight gradient (dW9, gradient bucket 0) is ordered on the side stream behind
@@ -957,15 +1018,8 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
   auto dx_pre_bn = [&](const T* dY, int64_t lddy, const T* W, int64_t ldw, int K, int j) {
     GemmArgs<T> g{dY, lddy, W, ldw, B, H, K, Bp, H, 0, 1, 0};
     StoreEpi bn;
-    bn.mode = 2;
-    bn.part = (float2*)c.f(l.bnpart);
-    bn.ldp = H;
-    bn.Y = c.f(l.Y[j]);
-    bn.ldy = H;
-    bn.save = c.f(l.save[j]);
-    bn.gamma = prm + d.off[kBlk[j][2]];
-    bn.beta = prm + d.off[kBlk[j][3]];
-    bn.H = H;
+    bn.mode = 2, bn.part = (float2*)c.f(l.bnpart), bn.ldp = H, bn.Y = c.f(l.Y[j]), bn.ldy = H, bn.H = H;
+    bn.save = c.f(l.save[j]), bn.gamma = prm + d.off[kBlk[j][2]], bn.beta = prm + d.off[kBlk[j][3]];
     have_part = launch_gemm_bn<T>(g, c.f(c.slab_off), H, nullptr, bn, c.s);
     return have_part ? 1 : gemm_to_slabs(c, g, H);
   };
@@ -978,7 +1032,6 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     S = dx_pre_bn(c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
   }
   chain_mark();
-  const int64_t shadow_w[6] = {l.sE0, l.sE1, l.sE2, l.sD0, l.sD1, l.sD2};
   for (int i = 5; i >= 0; --i) {
     const int64_t slab = (int64_t)(i == 5 && xp.da5 ? xp.Bq : Bp) * H;
     const bool sum = S > 1;
@@ -987,7 +1040,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
                             prm + d.off[kBlk[i][3]], B, H, c.f(l.bnpart), sum ? c.f(l.DA) : nullptr, c.s);
     // bias-gradient partials go to this layer's own slice: their column sum runs on the side stream
     float* colp = c.f(l.colbwd) + (int64_t)i * l.colbwd_cap;
-    const bool sync = train && st.opt.sync_bn;
+    const bool sync = bw.train && st.opt.sync_bn;
     double* syncb = (double*)(c.ws + l.syncb);
     if (sync) {  // SyncBN: the batch-coupling sums of the backward over every rank's rows
       launch_bn_sync_pack(c.f(l.bnpart), B, H, 1, syncb, c.s);
@@ -996,7 +1049,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
     // (input layer, bf16: its only consumer is dWe0, which reads dY0 transposed -- written that way
     // by the same pass instead of through a transpose launch)
     const bool dyt = i == 0 && sizeof(T) == 2;
-    launch_bn_bwd_apply<T>(sum ? c.f(l.DA) : c.f(c.slab_off), c.f(l.Y[i]), H, c.f(l.bnpart), B, Bp, H, train,
+    launch_bn_bwd_apply<T>(sum ? c.f(l.DA) : c.f(c.slab_off), c.f(l.Y[i]), H, c.f(l.bnpart), B, Bp, H, bw.train,
                            c.f(l.save[i]), prm + d.off[kBlk[i][2]], prm + d.off[kBlk[i][3]], gr + d.off[kBlk[i][2]],
                            gr + d.off[kBlk[i][3]], c.t(l.dY[i]), colp, c.s, sync ? syncb : nullptr,
                            dyt ? c.t(l.dYT0) : nullptr, Bp);
@@ -1063,7 +1116,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
       S = gemm_to_slabs(c, GemmArgs<T>{dY, H, c.t(l.sD0), Lr, B, L, H, Bp, Lr, 0, 1, 0}, L);
       float* colh = c.f(l.colbwd) + 6 * l.colbwd_cap;
       launch_reparam_bwd<T>(c.f(c.slab_off), S, (int64_t)Bp * L, L, c.f(l.HD), b->eps, scal, B, Bp, L, c.t(l.dH),
-                            L2r, dmu_ext, dlv_ext, colh, c.s);
+                            L2r, bw.dmu_ext, bw.dlv_ext, colh, c.s);
       fork_flush(3 >= hold_from);
       side_work(3 >= hold_from, [&, colh] {
         launch_colsum(colh, Bp / kReparamRows, 2 * L, 2 * L, gr + d.off[MUB], gr + d.off[LVB], L, w.s);
@@ -1078,7 +1131,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
       gemm_to(w, GemmArgs<T>{dY, H, c.t(l.A[i - 1]), H, H, H, Bp, H, H, 0, 0, 0}, gr + d.off[kBlk[i][0]], nullptr, 0,
               H);
     });
-    S = dx_pre_bn(dY, H, c.t(shadow_w[i]), H, H, i - 1);
+    S = dx_pre_bn(dY, H, c.t(l.shadow(i)), H, H, i - 1);
     chain_mark();
   }
 }
@@ -1161,31 +1214,20 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   MaskBand bs{rn, cn, (float)(kSplitUnit * 1.01 + g3H + gH), ctl + DecodeCtl::kCounts, list, kBandShardCap};
   MaskBand be = bs;
   be.coef = (float)(2.0 * gH);
-  bs.tlist = (uint2*)(c.ws + l.s3tlist);
-  bs.tcount = (unsigned*)(c.ws + l.s3tcount);
-  bs.tfound = ctl + DecodeCtl::kTileFound;
-  bs.tslots = kBandTileSlots;
+  bs.tlist = (uint2*)(c.ws + l.s3tlist), bs.tcount = (unsigned*)(c.ws + l.s3tcount);
+  bs.tfound = ctl + DecodeCtl::kTileFound, bs.tslots = kBandTileSlots;
   MaskBand b1 = bs;
-  b1.coef = (float)(kSingleUnit * 1.01 + 2.0 * gH);
-  b1.drop_overflow = 1;
-  b1.tiles_done = ctl + DecodeCtl::kTilesSingle;
+  b1.coef = (float)(kSingleUnit * 1.01 + 2.0 * gH), b1.drop_overflow = 1, b1.tiles_done = ctl + DecodeCtl::kTilesSingle;
   HIP_OK(hipMemsetAsync(bs.tcount, 0, (size_t)tiles * 4, c.s));
   // band-list overflow: entries past a shard's capacity flag their 256 x 256 block, which
   // k_band_tile_fix then recomputes whole in fp64 (no bit is left as a bf16 tier decided it)
   unsigned* ovf = (unsigned*)(c.ws + l.s3ovf);
   HIP_OK(hipMemsetAsync(ovf + Layout::kOvfCount, 0, (size_t)(Layout::kOvfFlags - Layout::kOvfCount + tiles) * 4, c.s));
   bs.cap = (unsigned)std::min<int>(opts().band_cap, (int)kBandShardCap);
-  bs.oflag = ovf + Layout::kOvfFlags;
-  bs.olist = bs.oflag + tiles;
-  bs.ocount = ovf + Layout::kOvfCount;
-  bs.obn = Gq / 256;
-  bs.oblocks = (unsigned)tiles;
-  be.cap = bs.cap;
-  be.oflag = bs.oflag;
-  be.olist = bs.olist;
-  be.ocount = bs.ocount;
-  be.obn = bs.obn;
-  be.oblocks = bs.oblocks;
+  bs.oflag = ovf + Layout::kOvfFlags, bs.olist = bs.oflag + tiles, bs.ocount = ovf + Layout::kOvfCount;
+  bs.obn = Gq / 256, bs.oblocks = (unsigned)tiles;
+  be.cap = bs.cap, be.oflag = bs.oflag, be.olist = bs.olist, be.ocount = bs.ocount;
+  be.obn = bs.obn, be.oblocks = bs.oblocks;
   const int on = single ? 1 : 0;
   const double single_bound = opts().single_bound_milli * 1e-3;  // (GM2_OPT_SAMPLE_SINGLE_BOUND, for A/Bs and tests)
   GemmArgs<bf16_t> g{a3, 2 * H, w3, 2 * H, n, G, 2 * H, Bq, Gq, 0};
@@ -1212,34 +1254,26 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   return true;
 }
 
+// where a sampling decode writes: u8 masks [n][ldm] or packed bits [n][ldb], and / or probabilities
+struct DecodeOut {
+  uint8_t *mask = nullptr, *bits = nullptr;
+  float* probs = nullptr;
+  int64_t ldm = 0, ldb = 0, ldpr = 0;
+};
+
+// Z [n][Lr] (in the workspace) -> the decoder half -> the output layer's masks / probabilities
 template <typename T>
-void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, uint8_t* mask, int64_t ldm, float* probs,
-                  int64_t ldpr, uint8_t* bits = nullptr, int64_t ldb = 0) {
+void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, const DecodeOut& o) {
   const Dims& d = c.d;
   const Layout& l = c.lo;
   const int Bp = (int)round_up(n, kTile), H = (int)d.H;
-  const T* in = c.t(l.Z);
-  int64_t ldin = d.Lr;
-  int Kin = (int)d.Lp;
-  int64_t ldw = d.Lr;
-  const int64_t shadow_in[3] = {l.sD0, l.sD1, l.sD2};
-  for (int j = 0; j < 3; ++j) {
-    const int i = 3 + j;
-    linear_pre_bn<T>(c, in, ldin, Bp, c.t(shadow_in[j]), ldw, n, H, Kin, prm + d.off[kBlk[i][1]], c.f(l.Y[i]),
-                     c.f(l.bnpart), false);
-    launch_bn_fwd_apply<T>(c.f(l.Y[i]), H, c.f(l.bnpart), n, Bp, H, 0, prm + d.off[kBlk[i][2]], prm + d.off[kBlk[i][3]],
-                           bn + (int64_t)i * 2 * H, bn + (int64_t)i * 2 * H + H, nullptr, c.t(l.A[i]), c.s);
-    in = c.t(l.A[i]);
-    ldin = H;
-    Kin = H;
-    ldw = H;
-  }
+  decoder_half<T>(c, BnPass{prm, bn, n, Bp});
   if constexpr (std::is_same_v<T, float>) {
-    if (!probs && opts().sample_split && decode_split3(c, prm, n, mask, ldm, bits, ldb)) return;
+    if (!o.probs && opts().sample_split && decode_split3(c, prm, n, o.mask, o.ldm, o.bits, o.ldb)) return;
   }
   if (c.st) c.st->exact_decodes++;
   GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, n, (int)d.G, H, Bp, (int)d.Gp, 0};
-  launch_gemm_mask<T>(g, prm + d.off[D9B], mask, ldm, probs, ldpr, c.s, bits, ldb);
+  launch_gemm_mask<T>(g, prm + d.off[D9B], o.mask, o.ldm, o.probs, o.ldpr, c.s, o.bits, o.ldb);
 }
 
 // make `s` wait for a pending stage on `ws` and forget it (the caller is about to write slot 0)
@@ -1297,8 +1331,7 @@ void run_train(const Layout& lo, const gm2_batch* b, const float* prm, float* gr
                double* loss, void* ws, void* strm, WsState& st) {
   if (b->n == 0 && st.opt.sync_bn) {
     st.join((hipStream_t)strm);  // (it zeroes the whole gradient buffer)
-    if (st.slot.staged) HIP_OK(hipStreamWaitEvent((hipStream_t)strm, st.slot_done, 0));
-    st.slot.staged = false;
+    drop_stage(st, (hipStream_t)strm);
     sync_bn_no_rows(lo, gr, bn, loss, ws, (hipStream_t)strm, st);
     return;
   }
@@ -1309,49 +1342,44 @@ void run_train(const Layout& lo, const gm2_batch* b, const float* prm, float* gr
     st.x3_split += n;
     st.x3_exact += 5 - n;
   }
+  SlotState& ss = st.slot;
+  bool hit = false;
+  int slot = 0;
+  NextStage nx;
+  const gm2_batch* nb = nullptr;
   if (zero_copy_ok<T>(c, b)) {  // the resident matrix's rows in place: no gather, no staging
     c.ridx = (const int32_t*)((char*)ws + lo.ridx);
-    c.xres = (const T*)b->resident;
-    c.ld_xres = b->ld_resident;
-    c.xbres = b->resident_bits;
-    c.ld_xbres = b->ld_resident_bits;
+    c.xres = (const T*)b->resident, c.ld_xres = b->ld_resident;
+    c.xbres = b->resident_bits, c.ld_xbres = b->ld_resident_bits;
     c.res_rows = b->resident_rows + 1;
     drop_stage(st, c.s);
-    std::function<void(hipStream_t)> tail;
-    forward<T>(c, b, prm, bn, 1, 1, scal, loss, gr, nullptr, 0, nullptr, 0.5f, true, false, &tail);
-    backward<T>(c, b, prm, gr, scal, nullptr, nullptr, 1, nullptr, &tail);
-    return;
+  } else {
+    hit = ss.staged && ss.prec == lo.prec && ss.total == lo.total && ss.data == b->data && ss.ld == b->ld_data &&
+          ss.rows == b->rows && ss.n == b->n;
+    slot = hit ? ss.slot : 0;
+    drop_stage(st, c.s);
+    c.xo = slot ? lo.X1 : lo.X;
+    c.xbo = slot ? lo.XB1 : lo.XB;
+    nb = b->next;
   }
-  SlotState& ss = st.slot;
-  const bool hit = ss.staged && ss.prec == lo.prec && ss.total == lo.total && ss.data == b->data &&
-                   ss.ld == b->ld_data && ss.rows == b->rows && ss.n == b->n;
-  if (ss.staged) HIP_OK(hipStreamWaitEvent(c.s, st.slot_done, 0));
-  const int slot = hit ? ss.slot : 0;
-  c.xo = slot ? lo.X1 : lo.X;
-  c.xbo = slot ? lo.XB1 : lo.XB;
-  ss.staged = false;
-  NextStage nx;
-  const gm2_batch* nb = b->next;
   if (nb) {
     if (nb->n <= 0 || nb->n > lo.d.Bm) throw Gm2Error("next batch: rows %lld outside (0, batch_max]", (long long)nb->n);
     check_batch_data(nb, lo.d, "next batch");
-    nx.b = nb;
-    nx.xo = slot ? lo.X : lo.X1;
-    nx.xbo = slot ? lo.XB : lo.XB1;
-    nx.done = st.slot_done;
+    nx.b = nb, nx.done = st.slot_done;
+    nx.xo = slot ? lo.X : lo.X1, nx.xbo = slot ? lo.XB : lo.XB1;
   }
   std::function<void(hipStream_t)> tail;
-  forward<T>(c, b, prm, bn, 1, 1, scal, loss, gr, nullptr, 0, nullptr, 0.5f, true, hit, &tail);
-  backward<T>(c, b, prm, gr, scal, nullptr, nullptr, 1, nb ? &nx : nullptr, &tail);
+  FwdCall fw;
+  fw.train = fw.with_grad = 1, fw.scal = scal, fw.loss = loss, fw.grads = gr;
+  fw.norm_hdr = true, fw.staged = hit, fw.defer_tail = &tail;
+  forward<T>(c, b, prm, bn, fw);
+  BwdCall bw;
+  bw.next = nb ? &nx : nullptr, bw.fwd_tail = &tail;
+  backward<T>(c, b, prm, gr, scal, bw);
   if (nb) {
-    ss.staged = true;
-    ss.slot = slot ^ 1;
-    ss.data = nb->data;
-    ss.ld = nb->ld_data;
-    ss.rows = nb->rows;
-    ss.n = nb->n;
-    ss.prec = lo.prec;
-    ss.total = lo.total;
+    ss.staged = true, ss.slot = slot ^ 1;
+    ss.data = nb->data, ss.ld = nb->ld_data, ss.rows = nb->rows, ss.n = nb->n;
+    ss.prec = lo.prec, ss.total = lo.total;
   }
 }
 
@@ -1373,6 +1401,23 @@ int with_ws_joined(void* ws, void* stream, F&& f) {
   return with_ws(ws, [&](WsState& st) {
     st.join((hipStream_t)stream);
     f(st);
+  });
+}
+
+// The body of gm2_decode_mask and gm2_decode_bits (`packed`): z [n][L] through the decoder of an
+// f32 workspace
+int decode_rows(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
+                const DecodeOut& o, bool packed, void* ws, void* stream) {
+  return with_ws_joined(ws, stream, [&](WsState& st) {
+    const Layout lo = make_layout(d, GM2_F32);
+    if (n <= 0 || n > lo.d.Bm) throw Gm2Error("decode rows %lld outside (0, batch_max]", (long long)n);
+    const bool ld_short = packed ? o.ldb < gm2_packed_row_bytes(lo.d.G) : o.ldm < lo.d.G;
+    if (ld_short || (o.probs && o.ldpr < lo.d.G))
+      throw Gm2Error(packed ? "decode_bits: ld too small" : "decode: ld < G");
+    Ctx<float> c(lo, ws, stream, &st);
+    // z [n][L] -> Z [Bm][Lp] (pad columns stay zero from workspace init)
+    HIP_OK(hipMemcpy2DAsync(c.f(lo.Z), lo.d.Lr * 4, z, lo.d.L * 4, lo.d.L * 4, n, hipMemcpyDeviceToDevice, c.s));
+    decode_chain<float>(c, params, const_cast<float*>(bn_running), (int)n, o);
   });
 }
 
@@ -1412,13 +1457,11 @@ int gm2_workspace_init(const gm2_dims* d, int prec, void* ws, size_t ws_bytes, v
 int gm2_sync_shadows(const gm2_dims* d, int prec, const float* params, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {
     const Layout lo = make_layout(d, prec);
-    if (lo.prec == GM2_F32) {
-      Ctx<float> c(lo, ws, stream, &st);
-      launch_shadow_sync<float>(make_table(c), params, c.s);
-    } else {
-      Ctx<bf16_t> c(lo, ws, stream, &st);
-      launch_shadow_sync<bf16_t>(make_table(c), params, c.s);
-    }
+    by_precision(lo.prec, [&](auto tag) {
+      using T = decltype(tag);
+      Ctx<T> c(lo, ws, stream, &st);
+      launch_shadow_sync<T>(make_table(c), params, c.s);
+    });
   });
 }
 
@@ -1428,9 +1471,7 @@ int gm2_resident_layout(int64_t S, int64_t G, int prec, int64_t* ld, int64_t* ld
     if (S < 0 || S > INT32_MAX - 64 || G <= 0 || (prec != GM2_F32 && prec != GM2_BF16))
       throw Gm2Error("resident layout: S=%lld G=%lld prec=%d", (long long)S, (long long)G, prec);
     const int64_t l = round_up(G, 2 * kTile), r = round_up(S + 1, 64);
-    *ld = l;
-    *ld_bits = l / 32;
-    *rows_alloc = r;
+    *ld = l, *ld_bits = l / 32, *rows_alloc = r;
     *bytes = (size_t)(r * l * (prec == GM2_F32 ? 4 : 2));
     *bits_bytes = (size_t)(r * (l / 32) * 4);
   });
@@ -1450,12 +1491,11 @@ int gm2_resident_build(const uint8_t* data, int64_t ld_data, int64_t S, int64_t 
     // columns G.. ld-1 zero
     const uint8_t* src = S > 0 ? data : (const uint8_t*)out;
     const int64_t lds = S > 0 ? ld_data : 16;
-    if (prec == GM2_F32)
-      launch_gather_rows<float>(src, lds, nullptr, (int)S, (int)G, (float*)out, l, (int)l, (int)r, bits, lb,
-                                (hipStream_t)stream);
-    else
-      launch_gather_rows<bf16_t>(src, lds, nullptr, (int)S, (int)G, (bf16_t*)out, l, (int)l, (int)r, bits, lb,
-                                 (hipStream_t)stream);
+    by_precision(prec, [&](auto tag) {
+      using T = decltype(tag);
+      launch_gather_rows<T>(src, lds, nullptr, (int)S, (int)G, (T*)out, l, (int)l, (int)r, bits, lb,
+                            (hipStream_t)stream);
+    });
   });
 }
 
@@ -1463,8 +1503,9 @@ int gm2_train_fwd_bwd(const gm2_dims* d, int prec, const gm2_batch* batch, const
                       float* bn_running, const float* scalars, double* loss, void* ws, void* stream) {
   return with_ws(ws, [&](WsState& st) {
     const Layout lo = make_layout(d, prec);
-    if (lo.prec == GM2_F32) run_train<float>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
-    else run_train<bf16_t>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
+    by_precision(lo.prec, [&](auto tag) {
+      run_train<decltype(tag)>(lo, batch, params, grads, bn_running, scalars, loss, ws, stream, st);
+    });
   });
 }
 
@@ -1477,8 +1518,7 @@ int gm2_grad_norm(const gm2_dims* d, int prec, const float* params, const float*
     double* part = (double*)((char*)ws + lo.gradpart);
     float* clip = (float*)((char*)ws + lo.clip);
     NormAhead na;
-    na.hdr = (const int*)((char*)ws + lo.nahdr);
-    na.sq = (const double*)((char*)ws + lo.nasq);
+    na.hdr = (const int*)((char*)ws + lo.nahdr), na.sq = (const double*)((char*)ws + lo.nasq);
     na.lo0 = lo.d.off[E0W], na.hi0 = lo.d.off[E0B], na.lo9 = lo.d.off[D9W], na.hi9 = lo.d.off[D9B];
     launch_grad_stats(params, grads, n, scalars, part, nb, na, (hipStream_t)stream);
     launch_grad_finalize(part, nb, scalars, clip, loss + 3, na, (hipStream_t)stream);  // loss[3], loss[4]
@@ -1490,7 +1530,7 @@ int gm2_adam_step(const gm2_dims* d, int prec, float* params, const float* grads
   return with_ws_joined(ws, stream, [&](WsState& st) {
     const Layout lo = make_layout(d, prec);
     const float* clip = (const float*)((char*)ws + lo.clip);
-    auto run = [&](auto tag) {
+    by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
       Ctx<T> c(lo, ws, stream, &st);
       const TensorTable all = make_table(c, 1);
@@ -1503,18 +1543,10 @@ int gm2_adam_step(const gm2_dims* d, int prec, float* params, const float* grads
       float* qs = (float*)((char*)ws + lo.adamscal);
       launch_adam_fused<T>(table_range(all, 0, all.n - 2), grads, params, m, v, scalars, clip, c.s, 0, qs);
       WsState::QueuedAdam& q = st.qadam;
-      q.queued = true;
-      q.prec = lo.prec;
+      q.queued = true, q.prec = lo.prec;
       q.tt = table_range(all, all.n - 2, all.n);
-      q.g = grads;
-      q.p = params;
-      q.m = m;
-      q.v = v;
-      q.scal = qs;
-      q.clip = clip;
-    };
-    if (lo.prec == GM2_F32) run(float{});
-    else run(bf16_t{});
+      q.g = grads, q.p = params, q.m = m, q.v = v, q.scal = qs, q.clip = clip;
+    });
   });
 }
 
@@ -1524,33 +1556,27 @@ int gm2_eval_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const 
     const Layout lo = make_layout(d, prec);
     drop_stage(st, (hipStream_t)stream);  // these write input slot 0
     float* bn = const_cast<float*>(bn_running);  // eval mode never writes running stats
-    if (lo.prec == GM2_F32) {
-      Ctx<float> c(lo, ws, stream, &st);
-      c.x3 = lo.x3 && st.opt.train_split != 0;
+    by_precision(lo.prec, [&](auto tag) {
+      using T = decltype(tag);
+      Ctx<T> c(lo, ws, stream, &st);
+      c.x3 = lo.x3 && st.opt.train_split != 0;  // (x3_plan: f32 elements only)
       if (lo.x3) {  // GM2_TSTAT_*: the input layer and the output layer + loss
-        const X3Plan xp = x3_plan<float>(c, (int)batch->n);
+        const X3Plan xp = x3_plan<T>(c, (int)batch->n);
         st.x3_split += (int)xp.enc0 + (int)xp.loss;
         st.x3_exact += 2 - ((int)xp.enc0 + (int)xp.loss);
       }
-      forward<float>(c, batch, params, bn, 0, 0, scalars, loss, nullptr);
-    } else {
-      Ctx<bf16_t> c(lo, ws, stream, &st);
-      forward<bf16_t>(c, batch, params, bn, 0, 0, scalars, loss, nullptr);
-    }
+      FwdCall fw;
+      fw.scal = scalars, fw.loss = loss;
+      forward<T>(c, batch, params, bn, fw);
+    });
   });
 }
 
 int gm2_decode_mask(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* mask, int64_t ld_mask, float* probs, int64_t ld_probs, void* ws, void* stream) {
-  return with_ws_joined(ws, stream, [&](WsState& st) {
-    const Layout lo = make_layout(d, GM2_F32);
-    if (n <= 0 || n > lo.d.Bm) throw Gm2Error("decode rows %lld outside (0, batch_max]", (long long)n);
-    if (ld_mask < lo.d.G || (probs && ld_probs < lo.d.G)) throw Gm2Error("decode: ld < G");
-    Ctx<float> c(lo, ws, stream, &st);
-    // z [n][L] -> Z [Bm][Lp] (pad columns stay zero from workspace init)
-    HIP_OK(hipMemcpy2DAsync(c.f(lo.Z), lo.d.Lr * 4, z, lo.d.L * 4, lo.d.L * 4, n, hipMemcpyDeviceToDevice, c.s));
-    decode_chain<float>(c, params, const_cast<float*>(bn_running), (int)n, mask, ld_mask, probs, ld_probs);
-  });
+  DecodeOut o;
+  o.mask = mask, o.ldm = ld_mask, o.probs = probs, o.ldpr = ld_probs;
+  return decode_rows(d, params, bn_running, z, n, o, false, ws, stream);
 }
 
 int64_t gm2_packed_row_bytes(int64_t G) { return round_up(G, kTile) / 8; }
@@ -1585,6 +1611,10 @@ int gm2_mask_compact(const uint8_t* bits, int64_t n, int64_t ld_bits, const uint
 }
 
 namespace {
+// the gene count of packed rows: the kernels index bits with 32-bit integers
+void check_gene_count(const char* what, int64_t G) {
+  if (G < 1 || G > 0x7fffffff) throw Gm2Error("%s: G %lld outside [1, 2^31)", what, (long long)G);
+}
 // one operand of the bit-row cross products: n rows of pitch ld, 16-B aligned, covering G bits
 void check_bit_rows(const char* what, const char* name, const uint8_t* p, int64_t n, int64_t ld, int64_t G) {
   if (n < 0) throw Gm2Error("%s: negative row count of %s (%lld)", what, name, (long long)n);
@@ -1599,7 +1629,7 @@ void check_bit_rows(const char* what, const char* name, const uint8_t* p, int64_
 int gm2_mask_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b, int64_t nb, int64_t ldb, int64_t G,
                      int32_t* out, int64_t ldo, void* stream) {
   return guarded([&] {
-    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_cooccur: G %lld outside [1, 2^31)", (long long)G);
+    check_gene_count("mask_cooccur", G);
     check_bit_rows("mask_cooccur", "a", a, na, lda, G);
     check_bit_rows("mask_cooccur", "b", b, nb, ldb, G);
     if (ldo < nb) throw Gm2Error("mask_cooccur: ldo %lld < nb %lld", (long long)ldo, (long long)nb);
@@ -1613,7 +1643,7 @@ int gm2_mask_cooccur(const uint8_t* a, int64_t na, int64_t lda, const uint8_t* b
 int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* ref, int64_t nr, int64_t ldr, int64_t G,
                      int64_t* best, void* stream) {
   return guarded([&] {
-    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_nearest: G %lld outside [1, 2^31)", (long long)G);
+    check_gene_count("mask_nearest", G);
     check_bit_rows("mask_nearest", "q", q, nq, ldq, G);
     check_bit_rows("mask_nearest", "ref", ref, nr, ldr, G);
     if (nr == 0) throw Gm2Error("mask_nearest: no reference rows (nr = 0)");
@@ -1628,7 +1658,7 @@ int gm2_mask_nearest(const uint8_t* q, int64_t nq, int64_t ldq, const uint8_t* r
 int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, int64_t G, const int32_t* rows, int64_t n,
                          int64_t* counts, int accumulate, void* stream) {
   return guarded([&] {
-    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_gene_counts: G %lld outside [1, 2^31)", (long long)G);
+    check_gene_count("mask_gene_counts", G);
     if (n < 0) throw Gm2Error("mask_gene_counts: negative n (%lld)", (long long)n);
     check_bit_rows("mask_gene_counts", "bits", bits, n_rows, ld_bits, G);
     if (!rows && n > n_rows)
@@ -1646,7 +1676,7 @@ int gm2_mask_gene_counts(const uint8_t* bits, int64_t n_rows, int64_t ld_bits, i
 int gm2_mask_transpose(const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, uint8_t* out, int64_t ld_out,
                        void* stream) {
   return guarded([&] {
-    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_transpose: G %lld outside [1, 2^31)", (long long)G);
+    check_gene_count("mask_transpose", G);
     if (n > 0x7fffffff) throw Gm2Error("mask_transpose: n %lld outside [0, 2^31)", (long long)n);
     check_bit_rows("mask_transpose", "bits", bits, n, ld_bits, G);
     if (ld_out <= 0 || (ld_out & 15) || ld_out < (n + 7) / 8)
@@ -1667,7 +1697,7 @@ int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, in
                              const int32_t* feat_start, const int32_t* feat_end, int64_t F, int64_t* removed_bp,
                              int32_t* genes_removed, uint64_t* signature, void* stream) {
   return guarded([&] {
-    if (G < 1 || G > 0x7fffffff) throw Gm2Error("mask_minimized_stats: G %lld outside [1, 2^31)", (long long)G);
+    check_gene_count("mask_minimized_stats", G);
     if (F < 0 || F > 0x7fffffff) throw Gm2Error("mask_minimized_stats: F %lld outside [0, 2^31)", (long long)F);
     check_bit_rows("mask_minimized_stats", "bits", bits, n, ld_bits, G);
     if (((uintptr_t)feat_col | (uintptr_t)feat_start | (uintptr_t)feat_end) & 3)
@@ -1691,14 +1721,9 @@ int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, in
 
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
-  return with_ws_joined(ws, stream, [&](WsState& st) {
-    const Layout lo = make_layout(d, GM2_F32);
-    if (n <= 0 || n > lo.d.Bm) throw Gm2Error("decode rows %lld outside (0, batch_max]", (long long)n);
-    if (ld_bits < gm2_packed_row_bytes(lo.d.G) || (probs && ld_probs < lo.d.G)) throw Gm2Error("decode_bits: ld too small");
-    Ctx<float> c(lo, ws, stream, &st);
-    HIP_OK(hipMemcpy2DAsync(c.f(lo.Z), lo.d.Lr * 4, z, lo.d.L * 4, lo.d.L * 4, n, hipMemcpyDeviceToDevice, c.s));
-    decode_chain<float>(c, params, const_cast<float*>(bn_running), (int)n, nullptr, 0, probs, ld_probs, bits, ld_bits);
-  });
+  DecodeOut o;
+  o.bits = bits, o.ldb = ld_bits, o.probs = probs, o.ldpr = ld_probs;
+  return decode_rows(d, params, bn_running, z, n, o, true, ws, stream);
 }
 
 int gm2_recon_counts(const gm2_dims* d, int prec, const gm2_batch* batch, const float* params, const float* bn_running,
@@ -1710,13 +1735,13 @@ int gm2_recon_counts(const gm2_dims* d, int prec, const gm2_batch* batch, const 
     if (!counts) throw Gm2Error("recon_counts: counts required");
     HIP_OK(hipMemsetAsync(counts, 0, (size_t)batch->n * 3 * 4, (hipStream_t)stream));
     float* bn = const_cast<float*>(bn_running);  // eval mode never writes running stats
-    auto run = [&](auto tag) {
+    by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
       Ctx<T> c(lo, ws, stream, &st);
-      forward<T>(c, batch, params, bn, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, counts, threshold);
-    };
-    if (lo.prec == GM2_F32) run(float{});
-    else run(bf16_t{});
+      FwdCall fw;
+      fw.counts = counts, fw.thr = threshold;
+      forward<T>(c, batch, params, bn, fw);
+    });
   });
 }
 
@@ -1726,40 +1751,17 @@ int gm2_encode(const gm2_dims* d, int prec, const gm2_batch* batch, const float*
     const Layout lo = make_layout(d, prec);
     drop_stage(st, (hipStream_t)stream);  // these write input slot 0
     gm2_batch b = *batch;
-    auto run = [&](auto tag) {
+    b.eps = nullptr;  // (mu and logvar alone: no z is drawn)
+    by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
       Ctx<T> c(lo, ws, stream, &st);
-      const Dims& dd = c.d;
-      const int B = (int)b.n, Bp = (int)round_up(B, kTile), H = (int)dd.H, L = (int)dd.L;
-      if (B <= 0 || B > dd.Bm) throw Gm2Error("encode rows outside (0, batch_max]");
-      check_batch_data(&b, dd, "encode");
-      float* bn = const_cast<float*>(bn_running);
-      launch_gather_rows<T>(b.data, b.ld_data, b.rows, B, (int)dd.G, c.t(lo.X), dd.Gp, (int)dd.Gp, Bp, nullptr, 0,
-                            c.s);
-      const T* in = c.t(lo.X);
-      int64_t ldin = dd.Gp;
-      int Kin = (int)dd.Gp;
-      const int64_t sh[3] = {lo.sE0, lo.sE1, lo.sE2};
-      for (int i = 0; i < 3; ++i) {
-        linear_pre_bn<T>(c, in, ldin, Bp, c.t(sh[i]), Kin, B, H, Kin, params + dd.off[kBlk[i][1]], c.f(lo.Y[i]),
-                         c.f(lo.bnpart), false);
-        launch_bn_fwd_apply<T>(c.f(lo.Y[i]), H, c.f(lo.bnpart), B, Bp, H, 0, params + dd.off[kBlk[i][2]],
-                               params + dd.off[kBlk[i][3]], bn + (int64_t)i * 2 * H, bn + (int64_t)i * 2 * H + H,
-                               nullptr, c.t(lo.A[i]), c.s);
-        in = c.t(lo.A[i]);
-        ldin = H;
-        Kin = H;
-      }
-      const int S =
-          gemm_to_slabs(c, GemmArgs<T>{c.t(lo.A[2]), H, c.t(lo.sHD), H, B, 2 * L, H, Bp, (int)dd.L2r, 0}, 2 * L);
-      launch_reparam<T>(c.f(lo.slabs), S, (int64_t)Bp * 2 * L, L, params + dd.off[MUB], params + dd.off[LVB], nullptr,
-                        B, Bp, c.f(lo.HD), c.t(lo.Z), dd.Lr, nullptr, 0, 0, c.f(lo.klpart), c.s);
-      if (mu) HIP_OK(hipMemcpy2DAsync(mu, L * 4, c.f(lo.HD), 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
-      if (logvar)
-        HIP_OK(hipMemcpy2DAsync(logvar, L * 4, c.f(lo.HD) + L, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
-    };
-    if (lo.prec == GM2_F32) run(float{});
-    else run(bf16_t{});
+      const int B = (int)b.n;
+      if (B <= 0 || B > c.d.Bm) throw Gm2Error("encode rows outside (0, batch_max]");
+      check_batch_data(&b, c.d, "encode");
+      const BnPass p{params, const_cast<float*>(bn_running), B, (int)round_up(B, kTile)};
+      encoder_half<T>(c, &b, p, X3Plan{}, false);
+      copy_heads<T>(c, B, mu, logvar);
+    });
   });
 }
 
@@ -1810,17 +1812,14 @@ int gm2_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const float
     drop_stage(st, (hipStream_t)stream);  // these write input slot 0
     if (!probs || ld_probs < lo.d.G) throw Gm2Error("forward: probs required, ld_probs >= G");
     if (!batch->eps) throw Gm2Error("forward: eps required (model.py:102 draws it)");
-    auto run = [&](auto tag) {
+    by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
       Ctx<T> c(lo, ws, stream, &st);
-      forward<T>(c, batch, params, bn_running, train, 0, nullptr, nullptr, nullptr, probs, ld_probs);
-      const int64_t L = lo.d.L, B = batch->n;
-      if (mu) HIP_OK(hipMemcpy2DAsync(mu, L * 4, c.f(lo.HD), 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
-      if (logvar)
-        HIP_OK(hipMemcpy2DAsync(logvar, L * 4, c.f(lo.HD) + L, 2 * L * 4, L * 4, B, hipMemcpyDeviceToDevice, c.s));
-    };
-    if (lo.prec == GM2_F32) run(float{});
-    else run(bf16_t{});
+      FwdCall fw;
+      fw.train = train, fw.probs = probs, fw.ld_probs = ld_probs;
+      forward<T>(c, batch, params, bn_running, fw);
+      copy_heads<T>(c, batch->n, mu, logvar);
+    });
   });
 }
 
@@ -1831,7 +1830,7 @@ int gm2_backward_outputs(const gm2_dims* d, int prec, const gm2_batch* batch, co
     const Layout lo = make_layout(d, prec);
     drop_stage(st, (hipStream_t)stream);  // these write input slot 0
     if (!probs || !dprobs || ld_probs < lo.d.G) throw Gm2Error("backward_outputs: probs / dprobs required");
-    auto run = [&](auto tag) {
+    by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
       Ctx<T> c(lo, ws, stream, &st);
       const Dims& dd = c.d;
@@ -1843,10 +1842,10 @@ int gm2_backward_outputs(const gm2_dims* d, int prec, const gm2_batch* batch, co
       // the fused loss terms are absent here: beta = 0 in a private scalar block
       float* scal0 = c.f(lo.scal0);
       HIP_OK(hipMemsetAsync(scal0, 0, GM2_NUM_SCALARS * 4, c.s));
-      backward<T>(c, batch, params, grads, scal0, dmu, dlogvar, train);
-    };
-    if (lo.prec == GM2_F32) run(float{});
-    else run(bf16_t{});
+      BwdCall bw;
+      bw.dmu_ext = dmu, bw.dlv_ext = dlogvar, bw.train = train;
+      backward<T>(c, batch, params, grads, scal0, bw);
+    });
   });
 }
 
@@ -1909,8 +1908,7 @@ int gm2_workspace_join(void* ws, void* stream) {
 int gm2_workspace_set_collective(void* ws, gm2_allreduce_fn fn, void* user) {
   return guarded([&] {
     WsState& st = ws_state(ws);
-    st.coll = fn;
-    st.coll_user = user;
+    st.coll = fn, st.coll_user = user;
   });
 }
 

@@ -523,6 +523,26 @@ def test_encode_row_list(prec):
     assert torch.equal(m.bn, bn0)
 
 
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
+def test_encode_matches_eval_forward_bitwise(prec):
+    """gm2_encode and gm2_forward(train=0) run the same encoder schedule (same gather, same GEMM plans,
+    running statistics in both; mu / logvar do not depend on eps): on one workspace, the same
+    parameters and the same rows, their mu and logvar are bit-identical (shape A)."""
+    tag = "A"
+    G, _, L, _, n = SHAPES[tag]
+    m, ws, mat, rows = _model(tag, _prec(prec))
+    batch = native.make_batch(mat.data, mat.ld, rows, n, _state(tag)["eps"].cuda())
+    mu_e, lv_e = torch.full((n, L), SENT, device="cuda"), torch.full((n, L), SENT, device="cuda")
+    native.encode(ws, batch, m.params, m.bn, mu_e, lv_e)
+    probs = torch.empty((n, G), device="cuda")
+    mu_f, lv_f = torch.full((n, L), SENT, device="cuda"), torch.full((n, L), SENT, device="cuda")
+    native.forward(ws, batch, m.params, m.bn, 0, probs, G, mu_f, lv_f)
+    torch.cuda.synchronize()
+    assert not (mu_e == SENT).any() and not (lv_e == SENT).any()
+    assert torch.equal(mu_e, mu_f), f"mu differs: max |d| {float((mu_e - mu_f).abs().max()):.3g}"
+    assert torch.equal(lv_e, lv_f), f"logvar differs: max |d| {float((lv_e - lv_f).abs().max()):.3g}"
+
+
 # ------------------------------------------------------------------------------------------------
 # h. gm2_reparameterize
 # ------------------------------------------------------------------------------------------------
