@@ -1171,15 +1171,13 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   if (!l.s3a || H % 32) return false;
   if ((((uintptr_t)(prm + d.off[D9W])) | ((uintptr_t)c.f(l.A[5]))) & 15) return false;
   if (bits && ((ldb & 15) || (((uintptr_t)bits) & 15) || ldb * 8 < d.Gp)) return false;
-  if (mask && !bits && (ldm < G)) return false;
-  // u8 masks alone: the decode writes packed bits into the workspace and k_expand_bits writes the
-  // caller's rows from them in one streaming pass (the tile epilogue's own u8 rows, at odd G never
-  // 16-B aligned, cost 3.4 ms more per 65,536-genome chunk, profiles/r06_decode_u8_ab.txt)
-  uint8_t* mask_out = nullptr;
+  if (mask && ldm < G) return false;
+  // u8 masks: the decode writes packed bits only (into the workspace when the caller wants none) and
+  // k_expand_bits writes the caller's rows from them in one streaming pass (the tile epilogue's own
+  // u8 rows, at odd G never 16-B aligned, cost 3.4 ms more per 65,536-genome chunk,
+  // profiles/r06_decode_u8_ab.txt)
   if (mask && !bits) {
     if (!l.s3bits || l.s3ldb * 8 < d.Gp) return false;
-    mask_out = mask;
-    mask = nullptr;
     bits = (uint8_t*)(c.ws + l.s3bits);
     ldb = l.s3ldb;
   }
@@ -1234,23 +1232,21 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   const MaskGate gs{ablk, wblk, 1, ctl + DecodeCtl::kTilesSplit, on, single_bound};
   if (single) {  // both bf16 tiers in one launch (a single tile whose band overflows re-runs as split)
     GemmArgs<bf16_t> g1{a1, H, w1, H, n, G, H, Bq, Gq, 0};
-    launch_gemm_mask_tiered(g1, g, prm + d.off[D9B], mask, ldm, bits, ldb, c.s,
+    launch_gemm_mask_tiered(g1, g, prm + d.off[D9B], bits, ldb, c.s,
                             MaskGate{ablk, wblk, 3, ctl + DecodeCtl::kTilesSingle, on, single_bound}, b1, gs, bs);
   } else {
-    launch_gemm_mask<bf16_t>(g, prm + d.off[D9B], mask, ldm, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
+    launch_gemm_mask<bf16_t>(g, prm + d.off[D9B], nullptr, 0, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
                              true, gs, bs);
   }
   GemmArgs<float> ge{c.f(l.A[5]), H, c.f(l.sD3), H, n, G, H, (int)round_up(n, kTile), (int)d.Gp, 0};
-  launch_gemm_mask<float>(ge, prm + d.off[D9B], mask, ldm, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
+  launch_gemm_mask<float>(ge, prm + d.off[D9B], nullptr, 0, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
                           false, MaskGate{ablk, wblk, 2, ctl + DecodeCtl::kTilesExact, on, single_bound}, be);
-  launch_band_fix(bs, tiles, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, bits, ldb, mask, ldm,
-                  ctl + DecodeCtl::kFlips, c.s);
-  launch_band_tile_fix(bs, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, n, G, bits, ldb, mask, ldm,
-                       ctl + DecodeCtl::kFlips, c.s);
+  launch_band_fix(bs, tiles, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, bits, ldb, ctl + DecodeCtl::kFlips, c.s);
+  launch_band_tile_fix(bs, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, n, G, bits, ldb, ctl + DecodeCtl::kFlips, c.s);
   launch_decode_stats(ctl + DecodeCtl::kTilesSplit, ctl + DecodeCtl::kTilesExact, ctl + DecodeCtl::kTilesSingle,
                       ctl + DecodeCtl::kCounts, ctl + DecodeCtl::kTileFound, ctl + DecodeCtl::kFlips, bs.cap,
                       (unsigned long long*)(ctl + DecodeCtl::kCum), bs.ocount, (unsigned long long*)ovf, c.s);
-  if (mask_out) launch_expand_bits(bits, ldb, n, G, mask_out, ldm, c.s);
+  if (mask) launch_expand_bits(bits, ldb, n, G, mask, ldm, c.s);
   return true;
 }
 

@@ -600,8 +600,7 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
 // its own store code: with the general one every 256x256 kernel spilled 12-21 VGPRs, with these
 // none): 0 = general (bias, BatchNorm statistics, row split, unaligned rows, transposed store),
 // 1 = plain fp32 store (split-K slabs or one pass, rows aligned or not, optional per-tile sums of
-// squares), 2 = the transposed store straight from the accumulators (+ sums of squares), 3 = the
-// transposed store through the LDS image (+ sums of squares)
+// squares), 2 = the transposed store through the LDS image (+ sums of squares)
 // S3 (PP only; GM2_BF16X3 training): both operands in the split layout of k_split_kmajor / k_split_rows
 // (g.K = twice the real K) and the main loop in its hi.hi + hi.lo + lo.hi form
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0, bool S3 = false>
@@ -632,7 +631,7 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
   // (the specialised epilogues: their options fixed, so the general code below folds away)
   const float* __restrict__ bias = EPI == 0 ? bias_in : nullptr;
   const int bmode = EPI == 0 ? bn.mode : 0;
-  const int btrans = EPI == 0 ? bn.trans : EPI >= 2;
+  const int btrans = EPI == 0 ? bn.trans : EPI == 2;
   const int kbeg = tl.split * g.k_per_split;
   const int kend = min(g.K, kbeg + g.k_per_split);
   const int nk = (kend - kbeg) / E<T>::KT;
@@ -695,37 +694,8 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
       bbeta[u] = fmaf(-bmean[u], balpha[u], bn.beta[n + u]);
     }
   }
-  // Transposed store straight from the accumulators (bn.trans_direct): lane l of fragment (mi, ni)
-  // holds rows m .. m + 3 (j) of column n, i.e. 16 contiguous bytes of C^T's row n -- one 16-B store
-  // per fragment, no LDS image and no barriers (each instruction writes 16 rows x 64 B; the L2 merges
-  // the two halves of each 128-B line, written by consecutive fragments)
-  const bool direct = EPI == 2;
-  if (direct) {
-#pragma unroll
-    for (int mi = 0; mi < C::FM; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < C::FN; ++ni) {
-        const int nn = tl.n0 + wn * C::WTN + ni * 16 + (lane & 15);
-        const int m = tl.m0 + wm * C::WTM + mi * 16 + 4 * (lane >> 4);
-        if (nn >= g.N) continue;
-        const f32x4 v = acc[mi][ni];
-        float* dst = C0 + (int64_t)nn * ldc + m;
-        if (m + 3 < g.M) {
-          *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-          sqa += sq4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (m + u < g.M) {
-              dst[u] = v[u];
-              sqa += (double)v[u] * v[u];
-            }
-        }
-      }
-  }
 #pragma unroll
   for (int h = 0; h < NBANDS; ++h) {
-    if (direct) break;
     if (wm == h / BPW) {
       const int mi0 = (h % BPW) * (BR / 16);
 #pragma unroll
@@ -918,7 +888,20 @@ __device__ __forceinline__ float bfi(int m, float a, float b) {
   return r;
 }
 
-template <class C, typename T, bool FAST, bool WG, bool GRAD>
+// the exact element: (logit l, target bit x) -> BCE term and p added to bce / psum; returns dl
+// (GRAD; else 0, and its arithmetic is gone)
+struct ExactElem { float e, p, dl; };
+template <bool GRAD>
+__device__ __forceinline__ ExactElem recon_exact(float l, bool x, float wgam) {
+  const float p = 1.0f / (1.0f + expf(-l));
+  const float e = x ? -fmaxf(logf(p), -100.f) : -fmaxf(log1pf(-p), -100.f);
+  if constexpr (!GRAD) return {e, p, 0.f};
+  const float omp = 1.0f - p;
+  const float dp = (p - (x ? 1.0f : 0.0f)) / fmaxf(omp * p, 1e-12f) + wgam;
+  return {e, p, dp * omp * p};
+}
+
+template <class C, typename T, bool FAST, bool GRAD>
 __device__ __forceinline__ void recon_tile(const f32x4 (&acc)[C::FM][C::FN], const uint32_t* __restrict__ xrow,
                                            int64_t ldxb, const float* bias_s, int N, int n0, int wm, int wn, int q,
                                            int c, float wgam, T* img, float& bce, float& psum,
@@ -998,38 +981,20 @@ __device__ __forceinline__ void recon_tile(const f32x4 (&acc)[C::FM][C::FN], con
           const f32x2_t s2 = {__builtin_amdgcn_fmed3f(t2.x * -1e12f, 0.0f, 1.0f),
                               __builtin_amdgcn_fmed3f(t2.y * -1e12f, 0.0f, 1.0f)};
           f32x2_t dl2 = r2 * s2;
-          if constexpr (WG) dl2 = f32x2_t{-wgam, -wgam} * t2 + dl2;
+          dl2 = f32x2_t{-wgam, -wgam} * t2 + dl2;
           dl4[2 * h] = dl2.x;
           dl4[2 * h + 1] = dl2.y;
         }
       } else {
+        const uint32_t xb = xw[mi >> 1] >> ((mi & 1) * 16);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (FAST) {
-          const int msk = __builtin_amdgcn_sbfe((int)xw[mi >> 1], (mi & 1) * 16 + j, 1);  // x ? -1 : 0
-          const float y = fmaf(acc[mi][ni][j], -1.4426950408889634f, bn[j]);  // -l log2 e
-          const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y));
-          const float nomp = p - 1.0f;  // -(1 - p)
-          const float arg = bfi(msk, p, nomp);  // x ? p : p - 1
-          bce_c += fmaxf(__builtin_amdgcn_logf(fabsf(arg)), -144.26950408889634f);  // max(log2, -100/ln 2)
-          ps_c += p;
-          const float r = bfi(msk, nomp, p);    // p - x
-          const float s = __builtin_amdgcn_fmed3f(nomp * -1e12f * p, 0.0f, 1.0f);
-          float dl = r * s;
-          if constexpr (WG) dl = fmaf(-wgam, nomp * p, dl);
-          dl4[j] = dl;
-        } else {
-          const uint32_t xb = xw[mi >> 1] >> ((mi & 1) * 16);
-          const bool x = (xb >> j) & 1u;
-          const float l = acc[mi][ni][j] + bn[j];
-          const float p = 1.0f / (1.0f + expf(-l));
-          bce_c += x ? -fmaxf(logf(p), -100.f) : -fmaxf(log1pf(-p), -100.f);
-          ps_c += p;
-          const float omp = 1.0f - p;
-          const float dp = (p - (x ? 1.0f : 0.0f)) / fmaxf(omp * p, 1e-12f) + wgam;
-          dl4[j] = dp * omp * p;
+        for (int j = 0; j < 4; ++j)
+        {
+          const ExactElem r = recon_exact<true>(acc[mi][ni][j] + bn[j], (xb >> j) & 1u, wgam);
+          bce_c += r.e;
+          ps_c += r.p;
+          dl4[j] = r.dl;
         }
-      }
       }
       if constexpr (GRAD) {
         if constexpr (sizeof(T) == 2) {
@@ -1138,8 +1103,8 @@ __device__ __forceinline__ void recon_loss_tile(const TileXY tl, const GemmArgs<
   // (one element loop with the gene-abundance FMA for every preset: at w*gamma = 0 it leaves dl bit
   // for bit as it was, costs half a packed FMA per element, and keeps the kernel to one copy of the
   // loop -- with a second, FMA-free copy behind a uniform branch it spilled 42 VGPRs, with one 4)
-  recon_tile<C, T, FAST, true, GRAD>(acc, xbits + ((tl.m0 + wm * C::WTM) >> 5), ldxb, bias_s, g.N, tl.n0, wm, wn, q, c,
-                                     wgam, img, bce, psum, xrows ? xidx : nullptr);
+  recon_tile<C, T, FAST, GRAD>(acc, xbits + ((tl.m0 + wm * C::WTM) >> 5), ldxb, bias_s, g.N, tl.n0, wm, wn, q, c, wgam,
+                               img, bce, psum, xrows ? xidx : nullptr);
   if constexpr (FAST) bce *= -0.6931471805599453f;
   GM2_STAMP(4);
   if constexpr (GRAD) {
@@ -1297,17 +1262,11 @@ __device__ __forceinline__ void recon_loss_tile_x3(const TileXY tl, const GemmAr
           for (int j = 0; j < 4; ++j) {
             if (gene0 + j >= g.M) continue;
             // (the reference's formula order, as the GM2_F32 kernel's exact path)
-            const bool x = (xw >> j) & 1u;
-            const float l = v[j] + bs[j];
-            const float p = 1.0f / (1.0f + expf(-l));
-            bce += x ? -fmaxf(logf(p), -100.f) : -fmaxf(log1pf(-p), -100.f);
-            psum += p;
-            if constexpr (GRAD) {
-              const float omp = 1.0f - p;
-              const float dp = (p - (x ? 1.0f : 0.0f)) / fmaxf(omp * p, 1e-12f) + wgam;
-              dl4[j] = dp * omp * p;
-              cs[j] += dl4[j];
-            }
+            const ExactElem r = recon_exact<GRAD>(v[j] + bs[j], (xw >> j) & 1u, wgam);
+            bce += r.e;
+            psum += r.p;
+            dl4[j] = r.dl;
+            if constexpr (GRAD) cs[j] += dl4[j];
           }
         }
         if constexpr (GRAD)
@@ -1650,38 +1609,6 @@ __device__ __forceinline__ void mask_tile(const TileXY tl, const GemmArgs<T>& g,
           *(uint4*)(o.bits + (int64_t)(tl.m0 + r) * o.ldb + tl.n0 / 8 + cc * 16) = *(const uint4*)(smem + r * BPR + cc * 16);
         }
       }
-      if (o.mask) {
-        // u8 masks expanded from the bit image (gm2_decode_mask): one lane per 4-B aligned dword of a
-        // row's 256-byte segment, so a wave instruction writes one row's bytes contiguously at any row
-        // alignment (the rows of a [n][G] mask are not 16-B aligned at odd G; the byte image's write-out
-        // took one byte store per element there); the partial dwords at the segment's two ends and at
-        // the gene edge by bytes (the neighbouring tiles own the rest of those dwords)
-        static_assert(BPR == 32, "eight bit words per tile row");
-        const int cols = min(C::BN, g.N - tl.n0);
-        for (int r = wid; r < rows; r += C::NT / 64) {
-          uint8_t* row = o.mask + (int64_t)(tl.m0 + r) * o.ldm + tl.n0;
-          const int a = (int)((uintptr_t)row & 3);
-          const uint32_t* bw = (const uint32_t*)(smem + r * BPR);
-          for (int k = lane; k < 64 + (a != 0); k += 64) {
-            const int c0 = 4 * k - a;  // tile column of the dword's first byte (-a at k = 0)
-            uint32_t x;                // its four mask bits
-            if (c0 < 0) {
-              x = (bw[0] << a) & 0xFu;
-            } else {
-              const int q = c0 >> 5;
-              const uint64_t w = (uint64_t)bw[q] | ((uint64_t)(q + 1 < 8 ? bw[q + 1] : 0u) << 32);
-              x = (uint32_t)(w >> (c0 & 31)) & 0xFu;
-            }
-            if (c0 >= 0 && c0 + 3 < cols) {
-              *(uint32_t*)(row + c0) = (x * 0x00204081u) & 0x01010101u;  // (row - a + 4k: aligned)
-            } else {
-#pragma unroll
-              for (int t = 0; t < 4; ++t)
-                if (c0 + t >= 0 && c0 + t < cols) row[c0 + t] = (uint8_t)((x >> t) & 1u);
-            }
-          }
-        }
-      }
       return;
     }
   }
@@ -1920,6 +1847,19 @@ static void ensure_lds_attr(const void* fn, int bytes) {
   done.insert({dev, fn});
 }
 
+// one launch with `lds` bytes of dynamic LDS, of a kernel whose launches take up to `lds_max`
+template <class K, class... A>
+static void launch_lds(K kernel, int grid, int threads, int lds_max, int lds, hipStream_t s, const A&... args) {
+  ensure_lds_attr((const void*)kernel, lds_max);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, args...);
+}
+
+// packed-bits output rows [m][ldb] that must cover `genes` bits
+static void check_bits_pitch(const uint8_t* bits, int64_t ldb, int genes) {
+  if (bits && ((ldb & 15) || (((uintptr_t)bits) & 15) || ldb * 8 < genes))
+    throw Gm2Error("mask bits: row pitch %lld must be a multiple of 16 bytes covering the padded genes", (long long)ldb);
+}
+
 // compute units of the current device (cached per device)
 static int device_cus() {
   static std::mutex mu;
@@ -1952,26 +1892,20 @@ static void store_launch_k(const GemmArgs<T>& a, int tiles, const StoreOut& o, c
   static_assert(C::LDS + table_max <= 160 * 1024, "LDS budget");
   const int lds = C::LDS + (IDX == 1 ? C::BM * 4 : IDX == 2 ? a.k_per_split * 4 : 0);
   if (lds > C::LDS + table_max) throw Gm2Error("gemm: %d bytes of LDS", lds);
-  ensure_lds_attr((const void*)k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>, C::LDS + table_max);
   StoreEpi ep = bn;
   GridCap gc{tiles, 0};
   if (bn.ntiles) gc = capped_grid(tiles, device_cus());  // the same number of rounds on fewer CUs
   ep.ntiles = gc.ntiles;
-  hipLaunchKernelGGL((k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>), dim3(gc.grid), dim3(C::NT), lds, s, a, o.C0,
-                     o.C1 ? o.C1 : o.C0, o.C1 ? o.msplit : (1 << 30), o.ldc, o.slab, o.bias, ep);
+  launch_lds(k_gemm_store<C, T, AK, BK, PP, IDX, EPI, S3>, gc.grid, C::NT, C::LDS + table_max, lds, s, a, o.C0,
+             o.C1 ? o.C1 : o.C0, o.C1 ? o.msplit : (1 << 30), o.ldc, o.slab, o.bias, ep);
 }
 
 // the specialised epilogue a 256x256 launch can take (k_gemm_store EPI): 1 = plain fp32 store,
-// 2 = transposed straight from the accumulators (env GM2_TRANS_DIRECT=1, A/B), 3 = transposed
-// through LDS, 0 = general
+// 2 = transposed through LDS, 0 = general
 static int store_epi(const GemmArgs<bf16_t>& a, const StoreOut& o, const StoreEpi& bn) {
-  static const bool trans_direct = [] {
-    const char* e = std::getenv("GM2_TRANS_DIRECT");
-    return e && e[0] == '1';
-  }();
   const bool aligned = ((o.ldc | o.slab) & 3) == 0 && (((uintptr_t)o.C0) & 15) == 0;
   if (o.bias || bn.mode || (o.C1 && o.msplit < a.M)) return 0;
-  if (bn.trans) return aligned ? (trans_direct ? 2 : 3) : 0;
+  if (bn.trans) return aligned ? 2 : 0;
   return 1;
 }
 
@@ -1979,8 +1913,9 @@ template <class C, typename T, bool AK, bool BK, bool PP, int IDX>
 static void store_launch_epi(const GemmArgs<T>& a, int tiles, const StoreOut& o, const StoreEpi& bn, hipStream_t s) {
   switch (store_epi(a, o, bn)) {
     case 1: return store_launch_k<C, T, AK, BK, PP, IDX, 1>(a, tiles, o, bn, s);
-    case 2: return store_launch_k<C, T, AK, BK, PP, IDX, 2>(a, tiles, o, bn, s);
-    case 3: return store_launch_k<C, T, AK, BK, PP, IDX, 3>(a, tiles, o, bn, s);
+    case 2:  // (launch_gemm_trans's one caller, the output-layer weight gradient, has no row table)
+      if constexpr (IDX == 0) return store_launch_k<C, T, AK, BK, PP, 0, 2>(a, tiles, o, bn, s);
+      throw Gm2Error("zero-copy rows: transposed store not instantiated");
     default: return store_launch_k<C, T, AK, BK, PP, IDX, 0>(a, tiles, o, bn, s);
   }
 }
@@ -2126,48 +2061,31 @@ int gemm_recon_row_tiles(const GemmArgs<T>& g) {  // strain tiles (rows of colpa
   return g.Np / (recon_big(g) ? 256 : 128);
 }
 
-template <class C, typename T, bool PP>
-static void recon_impl_k(const GemmArgs<T>& g, const float* bias, const uint32_t* X, int64_t ldx, int with_grad,
-                         const float* scal, T* dL, int64_t ldd, float* loss_part, float* colpart, int64_t ldcol,
-                         hipStream_t s, const int32_t* xrows) {
-  check_gemm(g, C::BM);
-  if (ldx * 32 < g.Mp || (ldx & 3)) throw Gm2Error("recon: target bit rows too short");
-  constexpr int lds = recon_lds_bytes<C, T>();
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  const GridCap gc = grid_for((g.Mp / C::BM) * (g.Np / C::BN), 4);
-  auto go = [&](auto kern) {
-    ensure_lds_attr((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(gc.grid), dim3(C::NT), lds, s, g, bias, X, ldx, gc.ntiles, scal, dL, ldd, loss_part,
-                       colpart, ldcol, xrows);
-  };
-  if (with_grad) go(k_gemm_recon_loss<C, T, PP, true>);
-  else go(k_gemm_recon_loss<C, T, PP, false>);
-}
-
-template <class C, typename T>
-static void recon_impl(const GemmArgs<T>& g, const float* bias, const uint32_t* X, int64_t ldx, int with_grad,
-                       const float* scal, T* dL, int64_t ldd, float* loss_part, float* colpart, int64_t ldcol,
-                       hipStream_t s, const int32_t* xrows) {
-  if constexpr (std::is_same_v<C, Big> && sizeof(T) == 2) {
-    if (pp_enabled())
-      return recon_impl_k<C, T, true>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
-  }
-  recon_impl_k<C, T, false>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
-}
-
 template <typename T>
 void launch_gemm_recon_loss(const GemmArgs<T>& g, const float* bias, const uint32_t* X, int64_t ldx, int with_grad,
                             const float* scal, T* dL, int64_t ldd, float* loss_part, float* colpart, int64_t ldcol,
                             hipStream_t s, const int32_t* xrows) {
   TimedLaunch tl(kKcReconLoss, s);
-  bool done = false;
+  // go(tile configuration, ping-pong main loop): the checks and the launch of that kernel
+  auto go = [&](auto cfg, auto pp) {
+    using C = decltype(cfg);
+    constexpr bool PP = decltype(pp)::value;
+    check_gemm(g, C::BM);
+    if (ldx * 32 < g.Mp || (ldx & 3)) throw Gm2Error("recon: target bit rows too short");
+    constexpr int lds = recon_lds_bytes<C, T>();
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    const GridCap gc = grid_for((g.Mp / C::BM) * (g.Np / C::BN), 4);
+    auto kern = with_grad ? k_gemm_recon_loss<C, T, PP, true> : k_gemm_recon_loss<C, T, PP, false>;
+    launch_lds(kern, gc.grid, C::NT, lds, lds, s, g, bias, X, ldx, gc.ntiles, scal, dL, ldd, loss_part, colpart, ldcol,
+               xrows);
+  };
+  bool big = false;
   if constexpr (sizeof(T) == 2) {
-    if (recon_big(g)) {
-      recon_impl<Big, T>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
-      done = true;
-    }
+    big = recon_big(g);
+    if (big && pp_enabled()) go(Big{}, std::true_type{});
+    else if (big) go(Big{}, std::false_type{});
   }
-  if (!done) recon_impl<Small, T>(g, bias, X, ldx, with_grad, scal, dL, ldd, loss_part, colpart, ldcol, s, xrows);
+  if (!big) go(Small{}, std::false_type{});
   GM2_CHECK_LAUNCH();
 }
 
@@ -2204,43 +2122,30 @@ void launch_gemm_recon_loss_x3(const GemmArgs<bf16_t>& g, const float* bias, con
   constexpr int lds = recon_x3_lds_bytes();
   static_assert(lds <= 160 * 1024, "LDS budget");
   const GridCap gc = grid_for((g.Mp / 256) * (g.Np / 256), 4);
-  auto go = [&](auto kern) {
-    ensure_lds_attr((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(gc.grid), dim3(Big::NT), lds, s, g, bias, X, ldx, gc.ntiles, scal, dL, ldd, gcols,
-                       drows, loss_part, colpart, ldcol);
-  };
-  if (with_grad) go(k_gemm_recon_loss_x3<true>);
-  else go(k_gemm_recon_loss_x3<false>);
+  launch_lds(with_grad ? k_gemm_recon_loss_x3<true> : k_gemm_recon_loss_x3<false>, gc.grid, Big::NT, lds, lds, s, g,
+             bias, X, ldx, gc.ntiles, scal, dL, ldd, gcols, drows, loss_part, colpart, ldcol);
   GM2_CHECK_LAUNCH();
 }
 
-void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* mask,
-                             int64_t ldm, uint8_t* bits, int64_t ldb, hipStream_t s, MaskGate gate1, MaskBand band1,
-                             MaskGate gate3, MaskBand band3) {
+void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* bits,
+                             int64_t ldb, hipStream_t s, MaskGate gate1, MaskBand band1, MaskGate gate3,
+                             MaskBand band3) {
   check_gemm(g1, 256);
   check_gemm(g3, 256);
   if (g1.Mp != g3.Mp || g1.Np != g3.Np || g1.Mp % 256 || g1.Np % 256 || g1.K % 64 || g3.K % 64)
     throw Gm2Error("tiered mask: the two GEMMs' tile grids differ");
-  if (bits && ((ldb & 15) || (((uintptr_t)bits) & 15) || ldb * 8 < g3.N))
-    throw Gm2Error("mask bits: row pitch %lld must be a multiple of 16 bytes covering the padded genes", (long long)ldb);
+  check_bits_pitch(bits, ldb, g3.N);
   if (!band1.rn || !band3.rn || !band1.tslots || !band3.tslots || !band1.drop_overflow || !gate3.run)
     throw Gm2Error("tiered mask: both bands with tile slots (the single tier's dropping its overflow) and the gate");
   if (!band3.oflag || !band3.olist || !band3.ocount || band3.obn < g3.Np / 256 ||
       band3.oblocks < (unsigned)((g3.Mp / 256) * band3.obn))
     throw Gm2Error("tiered mask: the overflow block flags, list and counter required");
-  const MaskOut o1{mask, ldm, bits, ldb, nullptr, 0, nullptr, nullptr, 0, 0.5f, gate1, band1};
-  const MaskOut o3{mask, ldm, bits, ldb, nullptr, 0, nullptr, nullptr, 0, 0.5f, gate3, band3};
+  const MaskOut o1{nullptr, 0, bits, ldb, nullptr, 0, nullptr, nullptr, 0, 0.5f, gate1, band1};
+  const MaskOut o3{nullptr, 0, bits, ldb, nullptr, 0, nullptr, nullptr, 0, 0.5f, gate3, band3};
   constexpr int lds = Big::LDS + band_lds_bytes<Big>();
-  const dim3 grid((g3.Mp / 256) * (g3.Np / 256));
   TimedLaunch tl(kKcMask, s);
-  auto go = [&](auto kern) {
-    ensure_lds_attr((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, grid, dim3(Big::NT), lds, s, g1, g3, bias, o1, o3);
-  };
-  // (packed bits and u8 masks both leave the bit-image epilogue: its ballots replace the byte image's
-  // per-element LDS stores; the u8 form through k_gemm_mask_tiered<..., false> measured 11.7 vs 5.3 ms
-  // per 65,536-genome chunk, profiles/r06_decode_u8_ab.txt)
-  go(k_gemm_mask_tiered<Big, bf16_t, true>);
+  launch_lds(k_gemm_mask_tiered<Big, bf16_t, true>, (g3.Mp / 256) * (g3.Np / 256), Big::NT, lds, lds, s, g1, g3, bias,
+             o1, o3);
   GM2_CHECK_LAUNCH();
 }
 
@@ -2250,8 +2155,7 @@ void launch_gemm_mask(const GemmArgs<T>& g, const float* bias, uint8_t* mask, in
                       float thr, bool big, MaskGate gate, MaskBand band) {
   check_gemm(g, big ? 256 : 128);
   // (the 256-column tiles may reach past the row pitch: their bits stores stop at ldb, past G)
-  if (bits && ((ldb & 15) || (((uintptr_t)bits) & 15) || ldb * 8 < (big ? g.N : g.Np)))
-    throw Gm2Error("mask bits: row pitch %lld must be a multiple of 16 bytes covering the padded genes", (long long)ldb);
+  check_bits_pitch(bits, ldb, big ? g.N : g.Np);
   if (counts && (!xbits || ldxb * 32 < g.Np)) throw Gm2Error("mask counts: target bits required");
   MaskOut o{mask, ldm, bits, ldb, probs, ldpr, counts, xbits, ldxb, thr, gate, band};
   if (band.rn && (!band.cn || !band.counts || !band.list || !band.cap || thr != 0.5f))
@@ -2268,11 +2172,8 @@ void launch_gemm_mask(const GemmArgs<T>& g, const float* bias, uint8_t* mask, in
       if (g.Mp % 256 || g.Np % 256 || g.K % 64) throw Gm2Error("mask (256x256): padded extents");
       static_assert(Big::LDS >= 256 * (256 + 16), "u8 image inside the staging ring");
       constexpr int lds_max = Big::LDS + band_lds_bytes<Big>();
-      const int lds = Big::LDS + band_lds;
-      const dim3 grid((g.Mp / 256) * (g.Np / 256));
       auto go = [&](auto kern) {
-        ensure_lds_attr((const void*)kern, lds_max);
-        hipLaunchKernelGGL(kern, grid, dim3(Big::NT), lds, s, g, bias, o);
+        launch_lds(kern, (g.Mp / 256) * (g.Np / 256), Big::NT, lds_max, Big::LDS + band_lds, s, g, bias, o);
       };
       const bool ballot = bits && !mask && !probs && !counts && thr == 0.5f;  // packed bits only: ballot epilogue
       if (ballot) go(k_gemm_mask<Big, T, true, true>);
@@ -2287,9 +2188,7 @@ void launch_gemm_mask(const GemmArgs<T>& g, const float* bias, uint8_t* mask, in
   if (gate.run) {  // (the tile loop, from a grid of at most 1024 workgroups)
     // (LDS: the band region always, then the verdict words)
     constexpr int lds = Small::LDS + band_lds_bytes<Small>() + (Small::NT / 64) * 8;
-    ensure_lds_attr((const void*)k_gemm_mask<Small, T, false, false, true>, lds);
-    hipLaunchKernelGGL((k_gemm_mask<Small, T, false, false, true>), dim3(std::min(ntile, 1024)), dim3(Small::NT), lds,
-                       s, g, bias, o);
+    launch_lds(k_gemm_mask<Small, T, false, false, true>, std::min(ntile, 1024), Small::NT, lds, lds, s, g, bias, o);
   } else {
     if (band_lds) ensure_lds_attr((const void*)k_gemm_mask<Small, T>, Small::LDS + band_lds_bytes<Small>());
     hipLaunchKernelGGL((k_gemm_mask<Small, T>), dim3(ntile), dim3(Small::NT), Small::LDS + band_lds, s, g, bias, o);

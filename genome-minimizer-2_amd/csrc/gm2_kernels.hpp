@@ -293,22 +293,21 @@ inline double band_gamma(double n) { return n * 0x1p-24 / (1.0 - n * 0x1p-24); }
 // the two bf16 tiers of the gated decode in one launch (gemm.hip k_gemm_mask_tiered): g1 / band1
 // the single product (K = H), g3 / band3 the bf16x3 split (K' = 2H), gate3 the verdicts (run 1) and
 // the split tiles' counter; gate1.tiles unused (band1.tiles_done counts the single tiles)
-void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* mask,
-                             int64_t ldm, uint8_t* bits, int64_t ldb, hipStream_t s, MaskGate gate1, MaskBand band1,
-                             MaskGate gate3, MaskBand band3);
+void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* bits,
+                             int64_t ldb, hipStream_t s, MaskGate gate1, MaskBand band1, MaskGate gate3,
+                             MaskBand band3);
 // k_band_fix over every shard's entries and every tile's slots: fp64 logit of (A[row], W[gene]) +
 // bias, mask bit = (float)logit > T (the correctly rounded fp32 logit against the reference's
-// threshold); packed bits (bits != nullptr) or u8 mask. flips: the bits it changed
+// threshold) in the packed bits. flips: the bits it changed
 void launch_band_fix(const MaskBand& band, int ntiles, const float* A, int64_t lda, const float* W, int64_t ldw,
-                     const float* bias, int H, uint8_t* bits, int64_t ldb, uint8_t* mask, int64_t ldm, unsigned* flips,
-                     hipStream_t s);
+                     const float* bias, int H, uint8_t* bits, int64_t ldb, unsigned* flips, hipStream_t s);
 // k_band_tile_fix over the blocks band.olist lists (band.ocount of them, read on the device): every
 // logit of rows [256 rb, min(256 rb + 256, n)) x genes [256 gb, min(.., G)) recomputed in fp64 as
-// k_band_fix does, the block's mask bits rewritten (packed: whole 32-bit words; pad genes 0), flips
+// k_band_fix does, the block's packed mask bits rewritten (whole 32-bit words; pad genes 0), flips
 // counted. Launched after launch_band_fix on a fixed grid (nothing to do = one load per workgroup).
 void launch_band_tile_fix(const MaskBand& band, const float* A, int64_t lda, const float* W, int64_t ldw,
-                          const float* bias, int H, int n, int G, uint8_t* bits, int64_t ldb, uint8_t* mask,
-                          int64_t ldm, unsigned* flips, hipStream_t s);
+                          const float* bias, int H, int n, int G, uint8_t* bits, int64_t ldb, unsigned* flips,
+                          hipStream_t s);
 // one workgroup: the decode call's per-call counters -> the workspace's cumulative ones (DecodeCtl);
 // ocount / ocum: the blocks k_band_tile_fix recomputed this call -> their cumulative count
 // packed mask bits [n][ldb] (bit g % 8 of byte g / 8) -> u8 [n][ldm] (0 / 1), any row alignment

@@ -1285,8 +1285,8 @@ __global__ __launch_bounds__(256) void k_exchange_unpack(const bf16_t* __restric
 // wave per listed (row, gene): logit = sum_k A[row][k] W[gene][k] in fp64 (each lane a strided
 // slice of k in order, then a fixed-order wave reduction: deterministic) + bias[gene]; the mask bit
 // becomes (float)logit > T, the correctly rounded fp32 logit against the reference's threshold.
-// Packed bits are set / cleared with 32-bit atomics (several waves may share a word), u8 masks by
-// byte stores. flips counts the bits the recompute changed.
+// Packed bits are set / cleared with 32-bit atomics (several waves may share a word). flips counts
+// the bits the recompute changed.
 // ---------------------------------------------------------------------------------------------
 // one band element per 16-lane group (four per wave): fp64 dot of the fp32 rows in a fixed order
 // (each lane a strided slice of float4s, then a fixed 16-lane tree) + bias; the group's first lane
@@ -1294,7 +1294,7 @@ __global__ __launch_bounds__(256) void k_exchange_unpack(const bf16_t* __restric
 __device__ __forceinline__ void band_fix_one(const uint2 rg, bool valid, int lane, const float* __restrict__ A,
                                              int64_t lda, const float* __restrict__ W, int64_t ldw,
                                              const float* __restrict__ bias, int H, uint8_t* bits, int64_t ldb,
-                                             uint8_t* mask, int64_t ldm, unsigned* flips) {
+                                             unsigned* flips) {
   const int q = lane & 15;
   double acc = 0.0;
   if (valid) {
@@ -1313,18 +1313,10 @@ __device__ __forceinline__ void band_fix_one(const uint2 rg, bool valid, int lan
   if (!valid || q != 0) return;
   acc += (double)bias[rg.y];
   const bool pred = (float)acc > kMaskLogitThreshold;
-  bool was;
-  if (bits) {
-    unsigned* word = (unsigned*)(bits + (int64_t)rg.x * ldb) + (rg.y >> 5);
-    const unsigned bit = 1u << (rg.y & 31);
-    const unsigned old = pred ? atomicOr(word, bit) : atomicAnd(word, ~bit);
-    was = (old & bit) != 0;
-  } else {
-    uint8_t* p = mask + (int64_t)rg.x * ldm + rg.y;
-    was = *p != 0;
-    *p = pred ? 1 : 0;
-  }
-  if (was != pred) atomicAdd(flips, 1u);
+  unsigned* word = (unsigned*)(bits + (int64_t)rg.x * ldb) + (rg.y >> 5);
+  const unsigned bit = 1u << (rg.y & 31);
+  const unsigned old = pred ? atomicOr(word, bit) : atomicAnd(word, ~bit);
+  if (((old & bit) != 0) != pred) atomicAdd(flips, 1u);
 }
 
 // workgroups [0, kBandFixShardWgs): the shards (wave w takes shard w % kBandShards, its entries
@@ -1336,8 +1328,7 @@ __device__ __forceinline__ void band_fix_one(const uint2 rg, bool valid, int lan
 constexpr int kBandFixShardWgs = 256;
 __global__ __launch_bounds__(256) void k_band_fix(MaskBand band, int ntiles, const float* __restrict__ A, int64_t lda,
                                                 const float* __restrict__ W, int64_t ldw, const float* __restrict__ bias,
-                                                int H, uint8_t* bits, int64_t ldb, uint8_t* mask, int64_t ldm,
-                                                unsigned* flips, int xcd) {
+                                                int H, uint8_t* bits, int64_t ldb, unsigned* flips, int xcd) {
   const int lane = threadIdx.x & 63, grp = lane >> 4;
   if (blockIdx.x < kBandFixShardWgs) {
     const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = kBandFixShardWgs * 4;
@@ -1347,8 +1338,7 @@ __global__ __launch_bounds__(256) void k_band_fix(MaskBand band, int ntiles, con
     const uint2* sl = band.list + (size_t)sh * band.cap;
     for (unsigned e0 = 4 * (wave / kBandShards); e0 < n; e0 += 4 * per) {
       const unsigned e = e0 + grp;
-      band_fix_one(e < n ? sl[e] : make_uint2(0u, 0u), e < n, lane, A, lda, W, ldw, bias, H, bits, ldb, mask, ldm,
-                   flips);
+      band_fix_one(e < n ? sl[e] : make_uint2(0u, 0u), e < n, lane, A, lda, W, ldw, bias, H, bits, ldb, flips);
     }
     return;
   }
@@ -1364,8 +1354,7 @@ __global__ __launch_bounds__(256) void k_band_fix(MaskBand band, int ntiles, con
   const uint2* tl = band.tlist + (size_t)t * band.tslots;
   for (unsigned e0 = 0; e0 < n; e0 += 4) {
     const unsigned e = e0 + grp;
-    band_fix_one(e < n ? tl[e] : make_uint2(0u, 0u), e < n, lane, A, lda, W, ldw, bias, H, bits, ldb, mask, ldm,
-                 flips);
+    band_fix_one(e < n ? tl[e] : make_uint2(0u, 0u), e < n, lane, A, lda, W, ldw, bias, H, bits, ldb, flips);
   }
 }
 
@@ -1382,8 +1371,7 @@ __global__ __launch_bounds__(256) void k_band_tile_fix(const unsigned* __restric
                                                      const float* __restrict__ A, int64_t lda,
                                                      const float* __restrict__ W, int64_t ldw,
                                                      const float* __restrict__ bias, int H, int rows_per, int n, int G,
-                                                     uint8_t* bits, int64_t ldb, uint8_t* mask, int64_t ldm,
-                                                     unsigned* flips) {
+                                                     uint8_t* bits, int64_t ldb, unsigned* flips) {
   extern __shared__ __attribute__((aligned(16))) float sa[];  // [rows_per][H]
   const int subs = 256 / rows_per, lane = threadIdx.x & 63;
   const unsigned nblk = min(*ocount, oblocks), items = nblk * (unsigned)subs;
@@ -1425,19 +1413,13 @@ __global__ __launch_bounds__(256) void k_band_tile_fix(const unsigned* __restric
       const int row = m0 + r;
       if (r >= rows_per || row >= n) continue;  // (uniform)
       const bool pred = g < G && (float)(acc[r] + b) > kMaskLogitThreshold;
-      if (bits) {
-        const uint64_t bal = __ballot(pred);
-        const int64_t byte = (int64_t)(g - lane) / 8 + 4 * (lane & 1);  // word (lane & 1) of the wave's 64 genes
-        if (lane < 2 && byte + 4 <= ldb) {
-          unsigned* word = (unsigned*)(bits + (int64_t)row * ldb + byte);
-          const unsigned v = (unsigned)(bal >> (32 * lane));
-          nflip += __popc(*word ^ v);
-          *word = v;
-        }
-      } else if (g < G) {
-        uint8_t* p = mask + (int64_t)row * ldm + g;
-        nflip += (*p != 0) != pred;
-        *p = pred ? 1 : 0;
+      const uint64_t bal = __ballot(pred);
+      const int64_t byte = (int64_t)(g - lane) / 8 + 4 * (lane & 1);  // word (lane & 1) of the wave's 64 genes
+      if (lane < 2 && byte + 4 <= ldb) {
+        unsigned* word = (unsigned*)(bits + (int64_t)row * ldb + byte);
+        const unsigned v = (unsigned)(bal >> (32 * lane));
+        nflip += __popc(*word ^ v);
+        *word = v;
       }
     }
   }
@@ -1728,10 +1710,8 @@ void launch_exchange_unpack(const bf16_t* in, int64_t n, float* x, hipStream_t s
 }
 
 void launch_band_fix(const MaskBand& band, int ntiles, const float* A, int64_t lda, const float* W, int64_t ldw,
-                     const float* bias, int H, uint8_t* bits, int64_t ldb, uint8_t* mask, int64_t ldm, unsigned* flips,
-                     hipStream_t s) {
-  if ((!bits && !mask) || (bits && (ldb & 3)))
-    throw Gm2Error("band fix: an output (packed bits with 4-B aligned rows, or a u8 mask) is required");
+                     const float* bias, int H, uint8_t* bits, int64_t ldb, unsigned* flips, hipStream_t s) {
+  if (!bits || (ldb & 3)) throw Gm2Error("band fix: packed bits with 4-byte aligned rows required");
   if (!band.counts || !band.list || !band.cap || ntiles < 0 || (ntiles && (!band.tlist || !band.tcount || band.tslots <= 0)))
     throw Gm2Error("band fix: shard list and counters (and tile slots for %d tiles) required", ntiles);
   // (a fixed grid for the shards, the counts live on the device: 16 waves per shard; then one wave per tile)
@@ -1740,8 +1720,8 @@ void launch_band_fix(const MaskBand& band, int ntiles, const float* A, int64_t l
   const unsigned grid = kBandFixShardWgs + (unsigned)((ntiles + 3) / 4);
   // env GM2_BANDFIX_LINEAR=1: tile quads in dispatch order (A/B of the XCD-aware order)
   static const int xcd = std::getenv("GM2_BANDFIX_LINEAR") ? 0 : 1;
-  hipLaunchKernelGGL(k_band_fix, dim3(grid), dim3(256), 0, s, band, ntiles, A, lda, W, ldw, bias, H, bits, ldb, mask,
-                     ldm, flips, xcd);
+  hipLaunchKernelGGL(k_band_fix, dim3(grid), dim3(256), 0, s, band, ntiles, A, lda, W, ldw, bias, H, bits, ldb, flips,
+                     xcd);
   GM2_CHECK_LAUNCH();
 }
 
@@ -1801,10 +1781,11 @@ void launch_decode_stats(const unsigned* tiles_split, const unsigned* tiles_exac
 }
 
 void launch_band_tile_fix(const MaskBand& band, const float* A, int64_t lda, const float* W, int64_t ldw,
-                          const float* bias, int H, int n, int G, uint8_t* bits, int64_t ldb, uint8_t* mask,
-                          int64_t ldm, unsigned* flips, hipStream_t s) {
-  if ((!bits && !mask) || (bits && (ldb & 3)) || H < 4 || H % 4 || (((uintptr_t)W | (uintptr_t)(ldw * 4)) & 15))
-    throw Gm2Error("band tile fix: packed bits with 4-B aligned rows or a u8 mask, H %% 4 == 0, 16-B aligned weight rows");
+                          const float* bias, int H, int n, int G, uint8_t* bits, int64_t ldb, unsigned* flips,
+                          hipStream_t s) {
+  if (!bits || (ldb & 3)) throw Gm2Error("band tile fix: packed bits with 4-byte aligned rows required");
+  if (H < 4 || H % 4 || (((uintptr_t)W | (uintptr_t)(ldw * 4)) & 15))
+    throw Gm2Error("band tile fix: H %% 4 == 0, 16-B aligned weight rows");
   if (!band.olist || !band.ocount || band.obn <= 0 || !band.oblocks || n < 0 || G < 0)
     throw Gm2Error("band tile fix: the overflow block list and counter required");
   // rows per work item: a power of two <= 16 whose fp32 rows fit 64 KB of LDS
@@ -1815,7 +1796,7 @@ void launch_band_tile_fix(const MaskBand& band, const float* A, int64_t lda, con
   // (<= 64 KB: within the default dynamic-LDS limit, no attribute needed)
   hipLaunchKernelGGL(k_band_tile_fix, dim3(512), dim3(256), lds, s, band.olist, band.ocount, band.obn, band.oblocks, A,
                      lda, W, ldw,
-                     bias, H, rows_per, n, G, bits, ldb, mask, ldm, flips);
+                     bias, H, rows_per, n, G, bits, ldb, flips);
   GM2_CHECK_LAUNCH();
 }
 
