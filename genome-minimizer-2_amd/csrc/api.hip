@@ -1715,6 +1715,116 @@ int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, in
   });
 }
 
+namespace {
+constexpr int64_t kSearchMaxK = 65536, kSearchMaxN = (int64_t)1 << 20, kSearchMaxG = (int64_t)1 << 23;
+constexpr int64_t kSearchMaxIndex = (int64_t)1 << 40;
+
+void check_search_k(const char* what, int64_t K) {
+  if (K < 1 || K > kSearchMaxK) throw Gm2Error("%s: K %lld outside [1, 65536]", what, (long long)K);
+}
+void check_search_genes(const char* what, int64_t G, int64_t n_groups) {
+  if (G < 1 || G >= kSearchMaxG) throw Gm2Error("%s: G %lld outside [1, 2^23)", what, (long long)G);
+  if (n_groups < 0 || n_groups > 0x7ffffffe) throw Gm2Error("%s: n_groups %lld outside [0, 2^31 - 1)", what, (long long)n_groups);
+}
+// the arrays of one state: all there, aligned, the rows pitched to cover G
+void check_search_state(const char* what, const char* name, const gm2_search_state* st, int64_t G) {
+  if (!st) throw Gm2Error("%s: null %s", what, name);
+  check_search_k(what, st->K);
+  if (!st->keys || !st->hashes || !st->essential || !st->rows || !st->count || !st->totals || !st->size_hist ||
+      !st->ess_hist || !st->error)
+    throw Gm2Error("%s: %s has a null array", what, name);
+  if (((uintptr_t)st->keys | (uintptr_t)st->hashes | (uintptr_t)st->totals | (uintptr_t)st->size_hist |
+       (uintptr_t)st->ess_hist) & 7)
+    throw Gm2Error("%s: the 64-bit arrays of %s must be 8-B aligned", what, name);
+  if (((uintptr_t)st->essential | (uintptr_t)st->count | (uintptr_t)st->error | (uintptr_t)st->z) & 3)
+    throw Gm2Error("%s: the 32-bit arrays of %s must be 4-B aligned", what, name);
+  if (st->ld_rows <= 0 || (st->ld_rows & 15) || st->ld_rows * 8 < G)
+    throw Gm2Error("%s: row pitch of %s (%lld) must be a multiple of 16 bytes covering G = %lld bits", what, name,
+                   (long long)st->ld_rows, (long long)G);
+  if ((uintptr_t)st->rows & 15) throw Gm2Error("%s: rows of %s must be 16-B aligned", what, name);
+  if (st->z && (st->L < 1 || st->ldz < st->L))
+    throw Gm2Error("%s: z of %s needs 1 <= L (%lld) <= ldz (%lld)", what, name, (long long)st->L, (long long)st->ldz);
+}
+// the two winner buffers of a fold: the same geometry, different memory
+void check_search_pair(const char* what, const gm2_search_state* in, const gm2_search_state* out, int64_t G) {
+  check_search_state(what, "state_in", in, G);
+  check_search_state(what, "state_out", out, G);
+  if (in == out || in->keys == out->keys || in->hashes == out->hashes || in->essential == out->essential ||
+      in->rows == out->rows || in->count == out->count || (in->z && in->z == out->z))
+    throw Gm2Error("%s: state_in and state_out must be two different winner buffers", what);
+  if (in->K != out->K || !in->z != !out->z || (in->z && in->L != out->L))
+    throw Gm2Error("%s: state_in and state_out differ in K, L or in having z", what);
+}
+}  // namespace
+
+int gm2_search_scratch_size(int64_t n_max, int64_t K, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Gm2Error("search_scratch_size: null bytes");
+    check_search_k("search_scratch_size", K);
+    if (n_max < 0 || n_max > kSearchMaxN)
+      throw Gm2Error("search_scratch_size: n_max %lld outside [0, 2^20]", (long long)n_max);
+    *bytes = search_scratch_bytes(n_max, K);
+  });
+}
+
+int gm2_search_init(const gm2_search_state* state, int64_t G, int64_t n_groups, void* stream) {
+  return guarded([&] {
+    check_search_genes("search_init", G, n_groups);
+    check_search_state("search_init", "state", state, G);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(hipMemsetAsync(state->count, 0, 4, s));
+    HIP_OK(hipMemsetAsync(state->error, 0, 4, s));
+    HIP_OK(hipMemsetAsync(state->totals, 0, 16, s));
+    HIP_OK(hipMemsetAsync(state->size_hist, 0, (size_t)(G + 1) * 8, s));
+    HIP_OK(hipMemsetAsync(state->ess_hist, 0, (size_t)(n_groups + 1) * 8, s));
+  });
+}
+
+int gm2_search_push(const gm2_search_state* state_in, const gm2_search_state* state_out, void* scratch,
+                    size_t scratch_bytes, const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, const float* z,
+                    int64_t ldz, int64_t base_index, const int32_t* group_offsets, int64_t n_groups,
+                    const int32_t* positions, int64_t min_groups, void* stream) {
+  return guarded([&] {
+    check_search_genes("search_push", G, n_groups);
+    check_search_pair("search_push", state_in, state_out, G);
+    if (n > kSearchMaxN) throw Gm2Error("search_push: n %lld outside [0, 2^20]", (long long)n);
+    check_bit_rows("search_push", "bits", bits, n, ld_bits, G);
+    if (base_index < 0 || base_index > kSearchMaxIndex - n)
+      throw Gm2Error("search_push: base index %lld outside [0, 2^40 - n]", (long long)base_index);
+    if (min_groups < 0) throw Gm2Error("search_push: negative min_groups (%lld)", (long long)min_groups);
+    if (n_groups && (!group_offsets || !positions)) throw Gm2Error("search_push: null group table with n_groups > 0");
+    if (((uintptr_t)group_offsets | (uintptr_t)positions | (uintptr_t)z) & 3)
+      throw Gm2Error("search_push: the group tables and z must be 4-B aligned");
+    if (n == 0) return;
+    if (!z != !state_in->z) throw Gm2Error("search_push: z is required exactly when the state keeps z");
+    if (z && ldz < state_in->L) throw Gm2Error("search_push: ldz %lld < L %lld", (long long)ldz, (long long)state_in->L);
+    if (!scratch || ((uintptr_t)scratch & 255)) throw Gm2Error("search_push: scratch must be 256-B aligned");
+    if (search_scratch_bytes(n, state_in->K) > scratch_bytes)
+      throw Gm2Error("search_push: scratch of %zu bytes, %zu needed (gm2_search_scratch_size)", scratch_bytes,
+                     search_scratch_bytes(n, state_in->K));
+    launch_search_push(*state_in, *state_out, scratch, bits, n, ld_bits, G, z, ldz, base_index, group_offsets, n_groups,
+                       positions, min_groups, (hipStream_t)stream);
+  });
+}
+
+int gm2_search_merge(const gm2_search_state* state_in, const gm2_search_state* state_out, void* scratch,
+                     size_t scratch_bytes, const gm2_search_state* other, int64_t G, int64_t n_groups, void* stream) {
+  return guarded([&] {
+    check_search_genes("search_merge", G, n_groups);
+    check_search_pair("search_merge", state_in, state_out, G);
+    check_search_state("search_merge", "other", other, G);
+    if (!other->z != !state_in->z || (other->z && other->L != state_in->L))
+      throw Gm2Error("search_merge: other differs from the state in L or in having z");
+    if (other->keys == state_in->keys || other->keys == state_out->keys || other->totals == state_out->totals)
+      throw Gm2Error("search_merge: other must not share arrays with the state");
+    if (!scratch || ((uintptr_t)scratch & 255)) throw Gm2Error("search_merge: scratch must be 256-B aligned");
+    if (search_scratch_bytes(other->K, state_in->K) > scratch_bytes)
+      throw Gm2Error("search_merge: scratch of %zu bytes, %zu needed (gm2_search_scratch_size)", scratch_bytes,
+                     search_scratch_bytes(other->K, state_in->K));
+    launch_search_merge(*state_in, *state_out, scratch, *other, G, n_groups, (hipStream_t)stream);
+  });
+}
+
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
   DecodeOut o;
@@ -1979,7 +2089,7 @@ int gm2_timing_class(int kernel_class, double* total_ms, int64_t* launches) {
 int gm2_debug_flags(unsigned* flags) {
   return guarded([&] {
     if (!flags) throw Gm2Error("null flags");
-    *flags = dbg_take_kernels() | dbg_take_gemm() | dbg_take_masks();
+    *flags = dbg_take_kernels() | dbg_take_gemm() | dbg_take_masks() | dbg_take_search();
   });
 }
 

@@ -12,6 +12,8 @@
 #include "gemm_plan.hpp"
 #include "gm2_common.hpp"
 
+struct gm2_search_state;  // include/gm2.h
+
 namespace gm2 {
 
 struct Gm2Error : std::runtime_error {
@@ -117,7 +119,11 @@ struct OptionScope {
 };
 
 // ---- live per-kernel timing (bench.py): hipEvent pairs around every launch of one class ----
-enum KernelClass { kKcReconLoss = 1, kKcGemmStore = 2, kKcMask = 4, kKcAdam = 8 };
+enum KernelClass {
+  kKcReconLoss = 1, kKcGemmStore = 2, kKcMask = 4, kKcAdam = 8,
+  // the stages of a search push (search.hip): row pass; table clear + insert + mark; radix select; gather
+  kKcSearchScore = 16, kKcSearchDedupe = 32, kKcSearchSelect = 64, kKcSearchGather = 128
+};
 void timing_begin(int classes);
 void timing_end(double* total_ms, int64_t* launches);
 // the last timed region's total for one class (after timing_end)
@@ -455,6 +461,18 @@ void launch_minimized_stats(const uint8_t* bits, int64_t n, int64_t ldb, int64_t
                             const int32_t* fstart, const int32_t* fend, int64_t F, int64_t* removed_bp,
                             int32_t* genes_removed, uint64_t* signature, hipStream_t s);
 
+// ---- search.hip: the running top-K of the smallest viable distinct packed rows (gm2.h gm2_search_*) ----
+// bytes of scratch for pushes of at most n_max rows into states of K entries
+size_t search_scratch_bytes(int64_t n_max, int64_t K);
+// out = the best of in and the chunk bits [n][ldb] (row r: global index base + r; z [n][ldz] or null); the
+// totals, histograms and error flag accumulate at out's pointers; the arguments are already checked
+void launch_search_push(const gm2_search_state& in, const gm2_search_state& out, void* scratch, const uint8_t* bits,
+                        int64_t n, int64_t ldb, int64_t G, const float* z, int64_t ldz, int64_t base,
+                        const int32_t* goff, int64_t ngroups, const int32_t* pos, int64_t min_groups, hipStream_t s);
+// out = the best of in and other's winners; other's totals, histograms and error are added to out's
+void launch_search_merge(const gm2_search_state& in, const gm2_search_state& out, void* scratch,
+                         const gm2_search_state& other, int64_t G, int64_t ngroups, hipStream_t s);
+
 // parameter tensor table for the multi-tensor optimizer / shadow kernels
 struct TensorDesc {
   int64_t off;        // offset in the flat fp32 param/grad/m/v buffers
@@ -503,6 +521,7 @@ int grad_stats_blocks(int64_t n);
 unsigned dbg_take_kernels();
 unsigned dbg_take_gemm();
 unsigned dbg_take_masks();
+unsigned dbg_take_search();
 #endif
 
 }  // namespace gm2

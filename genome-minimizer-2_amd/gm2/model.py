@@ -271,13 +271,20 @@ class VAE:
                                None if probs is None else probs[s:], G)
         return mask, probs
 
-    def decode_bits(self, z, want_probs=False, chunk=65536):
+    def decode_bits(self, z, want_probs=False, chunk=65536, out=None):
         """Like decode_mask, but the masks stay on the device packed 8 genes per byte
-        (gm2.masks.PackedMasks): what --mode sample hands to the mask consumers."""
+        (gm2.masks.PackedMasks): what --mode sample hands to the mask consumers. out: a PackedMasks of
+        at least N rows (from PackedMasks.empty) whose first N rows are written and returned instead of
+        a new set (a streaming caller's reused chunk buffer)."""
         from .masks import PackedMasks
         z = z.to(self.device, torch.float32).contiguous()
         N, G = z.shape[0], self.input_dim
-        pm = PackedMasks.empty(N, G, self.device)
+        if out is None:
+            pm = PackedMasks.empty(N, G, self.device)
+        else:
+            if out.G != G or out.n < N:
+                raise ValueError(f"decode_bits: out holds {out.n} rows of {out.G} genes, {N} of {G} needed")
+            pm = PackedMasks(out.bits[:N], G)
         probs = torch.empty(N, G, dtype=torch.float32, device=self.device) if want_probs else None
         for s in range(0, N, chunk):
             n = min(chunk, N - s)

@@ -39,9 +39,11 @@ EXPORTS = ["gm2_last_error", "gm2_abi_version", "gm2_param_count", "gm2_param_of
            "gm2_timing_begin", "gm2_timing_end", "gm2_timing_class", "gm2_workspace_stat",
            "gm2_exchange_pack", "gm2_exchange_ranksum", "gm2_exchange_unpack", "gm2_split_operand",
            "gm2_mask_cooccur", "gm2_mask_nearest", "gm2_mask_gene_counts", "gm2_mask_transpose",
-           "gm2_mask_minimized_stats"]
+           "gm2_mask_minimized_stats",
+           "gm2_search_scratch_size", "gm2_search_init", "gm2_search_push", "gm2_search_merge"]
 ABI_VERSION = 6
 KC_RECON_LOSS, KC_GEMM_STORE, KC_MASK, KC_ADAM = 1, 2, 4, 8
+KC_SEARCH_SCORE, KC_SEARCH_DEDUPE, KC_SEARCH_SELECT, KC_SEARCH_GATHER = 16, 32, 64, 128   # the stages of a search push
 OPT_GEMM_PP, OPT_SIDE_STREAM, OPT_RECON_TILE, OPT_SMALL_SPLIT, OPT_BN_EPILOGUE, OPT_SMALL_WAVES = 1, 2, 3, 4, 5, 6
 OPT_INPUT_CHUNKS, OPT_GRID_CAP, OPT_SYNC_BN, OPT_DEFER_OUTPUT_ADAM = 7, 9, 10, 11
 OPT_GRAD_BUCKETS = 15
@@ -78,6 +80,16 @@ Batch._fields_ = [("data", C.c_void_p), ("ld_data", C.c_int64), ("rows", C.c_voi
                   ("resident", C.c_void_p), ("ld_resident", C.c_int64), ("resident_bits", C.c_void_p),
                   ("ld_resident_bits", C.c_int64), ("resident_rows", C.c_int64), ("resident_prec", C.c_int)]
 
+
+class SearchState(C.Structure):
+    """gm2_search_state (gm2.h): device pointers of one winner buffer of the streaming search + its geometry."""
+    _fields_ = [("keys", C.c_void_p), ("hashes", C.c_void_p), ("essential", C.c_void_p), ("rows", C.c_void_p),
+                ("z", C.c_void_p), ("count", C.c_void_p), ("totals", C.c_void_p), ("size_hist", C.c_void_p),
+                ("ess_hist", C.c_void_p), ("error", C.c_void_p),
+                ("K", C.c_int64), ("ld_rows", C.c_int64), ("L", C.c_int64), ("ldz", C.c_int64)]
+
+
+SEARCH_MAX_K, SEARCH_MAX_N, SEARCH_MAX_G, SEARCH_MAX_INDEX = 65536, 1 << 20, 1 << 23, 1 << 40
 
 _lib = None
 
@@ -119,6 +131,12 @@ def lib():
         "gm2_mask_gene_counts": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i32, vp]),
         "gm2_mask_transpose": (C.c_int, [vp, i64, i64, i64, vp, i64, vp]),
         "gm2_mask_minimized_stats": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
+        "gm2_search_scratch_size": (C.c_int, [i64, i64, C.POINTER(C.c_size_t)]),
+        "gm2_search_init": (C.c_int, [C.POINTER(SearchState), i64, i64, vp]),
+        "gm2_search_push": (C.c_int, [C.POINTER(SearchState), C.POINTER(SearchState), vp, C.c_size_t, vp, i64, i64, i64,
+                                      vp, i64, i64, vp, i64, vp, i64, vp]),
+        "gm2_search_merge": (C.c_int, [C.POINTER(SearchState), C.POINTER(SearchState), vp, C.c_size_t,
+                                       C.POINTER(SearchState), i64, i64, vp]),
         "gm2_recon_counts": (C.c_int, [dp, i32, C.POINTER(Batch), vp, vp, C.c_float, vp, vp, vp]),
         "gm2_gemm": (C.c_int, [i32, i32, i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, vp]),
         "gm2_grad_bucket_bounds": (C.c_int, [dp, C.POINTER(C.c_int64)]),
@@ -418,6 +436,44 @@ def mask_minimized_stats(bits, n, ld_bits, G, feat_col, feat_start, feat_end, F,
     check(lib().gm2_mask_minimized_stats(ptr(bits), int(n), int(ld_bits), int(G), ptr(feat_col), ptr(feat_start),
                                          ptr(feat_end), int(F), ptr(removed_bp), ptr(genes_removed), ptr(signature),
                                          stream()), "gm2_mask_minimized_stats")
+
+
+def search_state(keys, hashes, essential, rows, z, count, totals, size_hist, ess_hist, error) -> SearchState:
+    """The descriptor of one winner buffer of the streaming search (gm2_search_state) over device tensors:
+    keys / hashes int64 [K] (the uint64s' bytes), essential int32 [K], rows uint8 [K, ld], z fp32 [K, L] or
+    None, count int32 [1], totals int64 [2], size_hist int64 [G + 1], ess_hist int64 [n_groups + 1], error
+    int32 [1]. The tensors stay alive as long as the descriptor."""
+    st = SearchState(keys.data_ptr(), hashes.data_ptr(), essential.data_ptr(), rows.data_ptr(),
+                     None if z is None else z.data_ptr(), count.data_ptr(), totals.data_ptr(), size_hist.data_ptr(),
+                     ess_hist.data_ptr(), error.data_ptr(), int(keys.shape[0]), int(rows.stride(0)),
+                     0 if z is None else int(z.shape[1]), 0 if z is None else int(z.stride(0)))
+    st._keep = (keys, hashes, essential, rows, z, count, totals, size_hist, ess_hist, error)
+    return st
+
+
+def search_scratch_size(n_max: int, K: int) -> int:
+    """Bytes of scratch for pushes of at most n_max rows into states of K entries (gm2_search_scratch_size)."""
+    n = C.c_size_t()
+    check(lib().gm2_search_scratch_size(int(n_max), int(K), C.byref(n)), "gm2_search_scratch_size")
+    return n.value
+
+
+def search_init(state: SearchState, G, n_groups):
+    check(lib().gm2_search_init(C.byref(state), int(G), int(n_groups), stream()), "gm2_search_init")
+
+
+def search_push(state_in: SearchState, state_out: SearchState, scratch, scratch_bytes, bits, n, ld_bits, G, z, ldz,
+                base_index, group_offsets, n_groups, positions, min_groups):
+    """state_out = the best of state_in and the n packed rows of the chunk (gm2_search_push)."""
+    check(lib().gm2_search_push(C.byref(state_in), C.byref(state_out), ptr(scratch), int(scratch_bytes), ptr(bits), int(n),
+                                int(ld_bits), int(G), ptr(z), int(ldz), int(base_index), ptr(group_offsets),
+                                int(n_groups), ptr(positions), int(min_groups), stream()), "gm2_search_push")
+
+
+def search_merge(state_in: SearchState, state_out: SearchState, scratch, scratch_bytes, other: SearchState, G, n_groups):
+    """state_out = the best of state_in and other's winners, other's totals added (gm2_search_merge)."""
+    check(lib().gm2_search_merge(C.byref(state_in), C.byref(state_out), ptr(scratch), int(scratch_bytes),
+                                 C.byref(other), int(G), int(n_groups), stream()), "gm2_search_merge")
 
 
 def recon_counts(ws: Workspace, batch: Batch, params, bn, threshold, counts):

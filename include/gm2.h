@@ -302,6 +302,75 @@ int gm2_mask_minimized_stats(const uint8_t* bits, int64_t n, int64_t ld_bits, in
                              const int32_t* feat_start, const int32_t* feat_end, int64_t F, int64_t* removed_bp,
                              int32_t* genes_removed, uint64_t* signature, void* stream);
 
+/* (ABI 6, additive) Streaming search for the smallest viable distinct genomes: a device-resident running
+ * top-K over any number of packed rows, pushed chunk by chunk. The reference's "find me a minimal genome"
+ * is focused sampling (main.py:351-370: 100 samples, the smallest, noise around it); this keeps the K
+ * smallest distinct genomes of everything screened, and only they ever leave the device.
+ *
+ * A row is VIABLE when its essential count (the integer of gm2_mask_count_groups: groups with any
+ * position set, empty groups never counting) is >= min_groups. Two rows are the SAME genome when their
+ * bytes are equal; the kernels decide that by the 64-bit row hash H = mix(mix(size) + sum over the 64-bit
+ * words w_i of the row's first roundup(G,128)/8 bytes of mix(w_i + (i + 1) * 0x9e3779b97f4a7c15)), mix the
+ * splitmix64 finalizer (the all-ones value is mapped to all-ones minus one): equal rows always compare
+ * equal, different rows compare equal with probability about 2^-64 per pair. Of one genome only the row
+ * with the lowest global index is ELIGIBLE. A row's key is size << 40 | global index (size = popcount of
+ * the row, G < 2^23, index < 2^40): the state keeps the min(K, eligible) smallest keys of everything
+ * pushed, in no particular order.
+ *
+ * gm2_search_state is a POD of device pointers (host struct, like gm2_batch) over caller-owned arrays:
+ * the first `count[0]` entries of keys / hashes / essential / rows / z are the winners. A push reads
+ * state_in's winners and writes state_out's (two different winner buffers: ping-pong); the stream totals
+ * (totals[0] = rows seen, totals[1] = viable rows, size_hist[s] = rows of s genes over ALL rows seen,
+ * ess_hist[e] = rows with essential count e) and the error flag are accumulated in place at state_out's
+ * pointers with 64-bit integer atomics (exact, independent of the order), so the two states of a ping-pong
+ * normally share them. error[0] != 0: the duplicate table's bounded probing was exhausted (never with the
+ * table sizes below; the results are then incomplete and the host should raise).
+ *
+ * Every call is stream-ordered; none allocates, synchronises or reads anything back. Scratch (256-B
+ * aligned) holds the chunk's keys / hashes / counts, the duplicate hash set (open addressing,
+ * >= 2 (K + n) slots, cleared per push) and the selection list. Per push: one pass over the chunk's row
+ * bytes (size, essential count, hash, totals), hash-set insert (64-bit CAS on the hash, min on the key),
+ * canonical marking, a single-workgroup radix select of the K smallest keys, a gather with 16-byte copies.
+ * Limits: 1 <= K <= 65536, 0 <= n <= 2^20 per push, 1 <= G < 2^23, 0 <= base_index, base_index + n <= 2^40;
+ * ld_bits / ld_rows multiples of 16 covering G, rows 16-B aligned, only the first roundup(G,128)/8 bytes
+ * of a row are read or written; z fp32 [n][ldz] rows of state L floats, required iff the state has z.
+ * The indices of everything pushed into (or merged into) one state must be distinct.
+ * Return < 0 (see the last-error message; the checks run on the host before any GPU call) on a null or
+ * inconsistent state, K outside [1, 65536], G outside [1, 2^23), negative n or n > 2^20, a bad pitch or
+ * alignment, a base index outside [0, 2^40 - n], null tables with n_groups > 0, a negative min_groups or
+ * n_groups, a scratch too small for (n, K), state_in == state_out. n == 0 is a no-op that returns 0 (the
+ * winners stay in state_in).
+ *   gm2_search_scratch_size  bytes of scratch for pushes of at most n_max rows (and merges of states of at
+ *                            most n_max entries) into states of K entries
+ *   gm2_search_init          count, totals, histograms (G + 1 and n_groups + 1 entries) and error zeroed
+ *   gm2_search_push          state_out = the best of state_in and the chunk bits [n][ld_bits], whose row r
+ *                            has global index base_index + r
+ *   gm2_search_merge         state_out = the best of state_in and the winners of `other` (their own keys'
+ *                            indices; other's totals, histograms and error are added to state_out's): the
+ *                            reduction of the states of several devices. other has the same G, L and
+ *                            n_groups, any K <= n_max, and is not modified. */
+typedef struct gm2_search_state {
+  uint64_t* keys;      /* [K] size << 40 | global index */
+  uint64_t* hashes;    /* [K] the row hash H */
+  int32_t* essential;  /* [K] */
+  uint8_t* rows;       /* [K][ld_rows] packed rows */
+  float* z;            /* [K][ldz] or NULL */
+  int32_t* count;      /* [1] winners held */
+  int64_t* totals;     /* [2] seen, viable */
+  int64_t* size_hist;  /* [G + 1] */
+  int64_t* ess_hist;   /* [n_groups + 1] */
+  int32_t* error;      /* [1] */
+  int64_t K, ld_rows, L, ldz;
+} gm2_search_state;
+int gm2_search_scratch_size(int64_t n_max, int64_t K, size_t* bytes);
+int gm2_search_init(const gm2_search_state* state, int64_t G, int64_t n_groups, void* stream);
+int gm2_search_push(const gm2_search_state* state_in, const gm2_search_state* state_out, void* scratch,
+                    size_t scratch_bytes, const uint8_t* bits, int64_t n, int64_t ld_bits, int64_t G, const float* z,
+                    int64_t ldz, int64_t base_index, const int32_t* group_offsets, int64_t n_groups,
+                    const int32_t* positions, int64_t min_groups, void* stream);
+int gm2_search_merge(const gm2_search_state* state_in, const gm2_search_state* state_out, void* scratch,
+                     size_t scratch_bytes, const gm2_search_state* other, int64_t G, int64_t n_groups, void* stream);
+
 /* calculate_reconstruction_metrics (training/evaluation/metrics.py:19-64) without materialising the
  * reconstruction: eval-mode model(x) of `batch` (eps given: the reference samples z there too), then
  * per strain counts[i] = (TP, FP, FN) of (recon > threshold) against the strain's genes. */
@@ -510,7 +579,10 @@ enum { GM2_TSTAT_SPLIT_GEMMS = 32, GM2_TSTAT_EXACT_GEMMS = 33 };
 typedef int (*gm2_allreduce_fn)(double* buf, int64_t count, void* stream, void* user);
 int gm2_workspace_set_collective(void* ws, gm2_allreduce_fn fn, void* user);
 
-enum { GM2_KC_RECON_LOSS = 1, GM2_KC_GEMM_STORE = 2, GM2_KC_MASK = 4, GM2_KC_ADAM = 8 };
+enum { GM2_KC_RECON_LOSS = 1, GM2_KC_GEMM_STORE = 2, GM2_KC_MASK = 4, GM2_KC_ADAM = 8,
+       /* (ABI 6, additive) the stages of gm2_search_push / gm2_search_merge: the row pass (size, essential
+        * count, hash, totals); the duplicate table's clear, insert and mark; the radix select; the gather */
+       GM2_KC_SEARCH_SCORE = 16, GM2_KC_SEARCH_DEDUPE = 32, GM2_KC_SEARCH_SELECT = 64, GM2_KC_SEARCH_GATHER = 128 };
 int gm2_timing_begin(int kernel_classes);
 int gm2_timing_end(double* total_ms, int64_t* launches);
 /* (ABI 6) after gm2_timing_end: the summed duration and launch count of ONE of the classes that were

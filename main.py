@@ -45,6 +45,11 @@ gene-major packed rows (gm2_mask_transpose, then gm2_mask_cooccur; gm2/linkage.p
 what convert-samples + --mode minimizer would make of every sampled genome -- genes removed, reduced
 length, duplicate group -- from the packed rows and the GenBank record's gene features
 (gm2_mask_minimized_stats; gm2/minsizes.py), without gene lists or FASTA.
+--keep-smallest K (sample mode, off by default; --min-essential M, --search-chunk C) turns sampling into a
+streaming search: --num-samples genomes are decoded chunk by chunk and only the K smallest distinct ones
+that carry at least M essential genes (default: all of them) are kept, on the device (gm2_search_push;
+gm2/search.py). The summary lines come from exact histograms over every genome screened; the winners'
+masks, table and z are written, the consumers above run on the K winners, and no full-set file exists.
 """
 import argparse
 import os
@@ -95,6 +100,13 @@ def parse_arguments(argv=None):
     p.add_argument("--minimized-fill", choices=["essentials", "none"], default="essentials",
                    help="sample mode, --minimized-sizes: keep every essential gene as convert-samples' "
                         "_with_essentials lists do (essentials) or only the sampled genes (none)")
+    p.add_argument("--keep-smallest", type=int, default=None, metavar="K",
+                   help="sample mode: stream --num-samples genomes and keep only the K smallest distinct ones that "
+                        "still have their essential genes (the full-set files are not written)")
+    p.add_argument("--min-essential", type=int, default=None, metavar="M",
+                   help="sample mode, --keep-smallest: essential genes a genome must carry (default: all of them)")
+    p.add_argument("--search-chunk", type=int, default=65536, metavar="C",
+                   help="sample mode, --keep-smallest: genomes decoded and screened per step")
     p.add_argument("--genome-path", type=str, default=None,
                    help="GenBank genome (default: <project root>/data/wild_type_sequence.gb)")
     p.add_argument("--output-dir", type=str, default="./minimized_genomes")
@@ -166,17 +178,22 @@ def detect_version(model_path):
     return None
 
 
-def focused_z(model, latent_dim, num_samples, noise_level, device):
-    """main.py:351-370: 100 default samples, the one with fewest genes, then its output-space
-    nearest sample's z (the same index); returns z* + noise_level * N(0, I) [num_samples, L]."""
+def focused_center(model, latent_dim, device):
+    """main.py:351-366: 100 default samples, the one with fewest genes, then its output-space
+    nearest sample's z (the same index) -> z* [1, L]."""
     import numpy as np
-    import torch
     from gm2.extras import sample_from_model
     binary_temp, cont_temp, z_temp = sample_from_model(model, latent_dim, 100, device)
     min_ones_index = np.argmin(binary_temp.sum(axis=1))
     dist = np.linalg.norm(cont_temp - cont_temp[min_ones_index], axis=1)
     closest = np.argmin(dist)
-    z_star = z_temp[closest].unsqueeze(0)
+    return z_temp[closest].unsqueeze(0)
+
+
+def focused_z(model, latent_dim, num_samples, noise_level, device):
+    """main.py:351-370: the centre z* of focused_center, then z* + noise_level * N(0, I) [num_samples, L]."""
+    import torch
+    z_star = focused_center(model, latent_dim, device)
     noise = torch.randn(num_samples, latent_dim, device=device) * noise_level
     return z_star + noise
 
@@ -324,6 +341,80 @@ def minimized_sizes(args, packed, sizes, path):
     return True
 
 
+def run_smallest_search(args, model, config, merged, essential_gene_positions, out_dir, device):
+    """--keep-smallest: --num-samples genomes streamed through gm2.search.search_smallest (its docstring
+    is the draw order: per chunk one torch.randn, scaled around focused_center's z* in focused mode), then
+    the K winners' summary, files and consumers. Under torchrun every rank streams its rank_slice with
+    global indices and a generator seeded shared_seed + rank, and rank 0 merges the gathered states."""
+    import numpy as np
+    import pandas as pd
+    import torch
+    from gm2.ddp import get_dist, rank_slice, rank_world, shared_seed
+    from gm2.search import SmallestSearch, hist_quantiles, search_smallest
+    K, N, mode, tag = args.keep_smallest, args.num_samples, args.sampling_mode, config.trainer_version
+    if K < 1 or K > 65536 or args.search_chunk < 1 or (args.min_essential is not None and args.min_essential < 0):
+        print("✗ --keep-smallest takes 1..65536, --search-chunk >= 1, --min-essential >= 0")
+        return False
+    dist = get_dist()
+    rank, world = rank_world(dist)
+    generator = None
+    if dist is not None:
+        seed = shared_seed(dist)
+        torch.cuda.manual_seed(seed)   # (the focused centre below: the same on every rank)
+        generator = torch.Generator(device=device)
+        generator.manual_seed(seed + rank)
+    center = focused_center(model, config.latent_dim, device) if mode == "focused" else None
+    lo, hi = rank_slice(N, rank, world)
+    search = search_smallest(model, hi - lo, K, essential_gene_positions, args.min_essential, chunk=args.search_chunk,
+                             z_center=center, noise_level=args.noise_level if center is not None else None,
+                             generator=generator, base_index=lo, return_search=True)
+    if dist is not None:
+        mine = search.state_tensors()
+        gathered = {}
+        for name, t in mine.items():
+            parts = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(parts, t.contiguous())
+            gathered[name] = parts
+        if rank != 0:
+            return True
+        for r in range(1, world):
+            other = SmallestSearch(search.G, K, essential_gene_positions, args.min_essential,
+                                   latent_dim=config.latent_dim, device=device, chunk_max=1)
+            other.load_state_tensors({name: parts[r] for name, parts in gathered.items()},
+                                     next_index=rank_slice(N, r, world)[1])
+            search.merge(other)
+    res = search.result()
+    print(f"\n✓ Sampling Results:\n- Screened genomes: {res.seen}")
+    q = hist_quantiles(res.size_hist)
+    if q is not None:
+        print(f"- Median genome size: {q[0]:.0f} genes\n- Genome size range: {q[1]:.0f} - {q[2]:.0f}")
+        e = hist_quantiles(res.ess_hist)
+        print(f"- Median essential genes: {e[0]:.0f}\n- Essential range: {e[1]:.0f} - {e[2]:.0f}")
+    print(f"- Viable genomes (>= {search.min_groups} of {search.n_groups} essential genes): {res.viable} of {res.seen}")
+    k = len(res.indices)
+    if k:
+        print(f"- Kept the {k} smallest distinct viable genomes: {res.sizes.min()} - {res.sizes.max()} genes")
+    else:
+        print("- No viable genome was found: nothing kept")
+    packed = res.masks
+    if k and (args.nearest_strains or args.pca or args.gene_frequencies or args.gene_linkage):
+        compare_with_strains(args, packed, res.sizes, merged, out_dir, tag)
+    if args.minimized_sizes and k and not minimized_sizes(args, packed, res.sizes,
+                                                          out_dir / f"{tag}_minimized_sizes_{mode}.csv"):
+        return False
+    if args.mask_dtype == "bits":
+        out = packed.to_host()
+    else:
+        out = packed.unpack(np.float64 if args.mask_dtype == "float64" else np.uint8)
+    np.save(out_dir / f"{tag}_smallest_{mode}.npy", out)
+    pd.DataFrame({"rank": np.arange(k), "sample": res.indices, "genome_size": res.sizes,
+                  "essential_genes": res.essential}).to_csv(out_dir / f"{tag}_smallest_{mode}.csv", index=False)
+    np.save(out_dir / f"{tag}_smallest_z_{mode}.npy", res.z.cpu().numpy())
+    print(f"- Smallest genomes: {out_dir / f'{tag}_smallest_{mode}.csv'}")
+    print(f"\n✓ SAMPLING COMPLETE!\n- Results saved to: {out_dir}")
+    return True
+
+
 def run_sampling(args):
     """main.py:219-446 without the reference's plots: load the checkpoint, decode in fp32, threshold,
     count essential genes, save masks (.npy) and the genes x samples CSV; --nearest-strains / --pca
@@ -362,6 +453,8 @@ def run_sampling(args):
     model = load_model(input_dim, config.hidden_dim, config.latent_dim, args.model_path)
     print(f"- Architecture: {input_dim} -> {config.hidden_dim} -> {config.latent_dim}")
     print(f"- Samples: {args.num_samples}\n- Mode: {args.sampling_mode}\n- Output: {out_dir}")
+    if args.keep_smallest is not None:
+        return run_smallest_search(args, model, config, merged, essential_gene_positions, out_dir, device)
     from gm2.ddp import gather_rows, get_dist, rank_slice, rank_world, shared_seed
     dist = get_dist()
     rank, world = rank_world(dist)
