@@ -276,7 +276,7 @@ struct Ctx {
   const Dims& d;
   int64_t slab_off, slab_cap;  // split-K scratch of this stream
   int64_t xo, xbo;             // input slot of this call: gathered rows X [Bm][Gp] (T), target bits
-  WsState* st;                 // host-side state of the workspace
+  WsState& st;                 // host-side state of the workspace
   // zero-copy rows (gm2_batch.resident, training calls): the input layer's GEMMs and the loss
   // epilogue read the resident matrix's rows through ridx [roundup(Bm, 256)] instead of X / XB
   const int32_t* ridx = nullptr;
@@ -287,7 +287,7 @@ struct Ctx {
   int64_t res_rows = 0;  // rows of the resident operands (their zero row included): bounds of ridx
   bool x3 = false;       // GM2_BF16X3 with GM2_OPT_TRAIN_SPLIT on: the G-wide GEMMs as split-bf16 products
   bf16_t* h(int64_t off) const { return (bf16_t*)(ws + off); }
-  Ctx(const Layout& l, void* w, void* strm, WsState* state = nullptr)
+  Ctx(const Layout& l, void* w, void* strm, WsState& state)
       : lo(l), ws((char*)w), s((hipStream_t)strm), d(l.d), slab_off(l.slabs), slab_cap(l.slab_cap), xo(l.X),
         xbo(l.XB), st(state) {}
   Ctx side(hipStream_t strm) const {
@@ -330,18 +330,32 @@ struct SlotState {
   int prec = -1;
 };
 
-// Events that only order this device's own streams (fork / join ring, staged input slot, deferred
-// update) release at device scope: a system-scope release writes the L2 back at every fork of the
-// backward (measured ~7 us of idle main stream per fork). The gradient-bucket events keep the
-// system-scope release (a collective's peers may read the buffer). Env GM2_EVENT_FENCE=system
-// restores it everywhere (A/B).
-unsigned order_event_flags() {
-  static const unsigned f = [] {
-    const char* e = std::getenv("GM2_EVENT_FENCE");
-    return (e && std::string(e) == "system") ? (unsigned)hipEventDisableTiming
-                                             : (unsigned)(hipEventDisableTiming | hipEventReleaseToDevice);
+// The schedule's environment knobs, for A/Bs (tools/ and profiles/ name them); read once per process.
+//  GM2_EVENT_FENCE=system: events that only order this device's own streams (fork / join ring, staged
+//    input slot, deferred update) release at system scope, as the gradient-bucket events always do (a
+//    collective's peers may read the buffer). Default device scope: a system-scope release writes the
+//    L2 back at every fork of the backward (measured ~7 us of idle main stream per fork).
+//  GM2_FORK_HOLD (3): the first layer of the backward whose own fork is taken (6 = every layer forks).
+//    The side work of the layers above it (5, 4, 3, the heads) would queue behind dW9 anyway: it goes
+//    with the fork of layer 2 instead, one ordering event in place of five (-7..-11 us per step,
+//    profiles/r03_fork_batch_ab.txt; holding layer 2 as well measured +15 us).
+//  GM2_DW9_AT (2): the kernel of the backward's chain behind which dW9 starts (output_weight_grad).
+//  GM2_TAIL_MAIN: the forward's tail launch stays on the caller's stream instead of going in front of
+//    dW9 on the side stream (profiles/r03_fwd_tail_side_ab.txt).
+struct SchedEnv {
+  unsigned order_event_flags;
+  int fork_hold, dw9_at;
+  bool tail_main;
+};
+const SchedEnv& sched_env() {
+  static const SchedEnv env = [] {
+    const char *fence = std::getenv("GM2_EVENT_FENCE"), *hold = std::getenv("GM2_FORK_HOLD");
+    const char* at = std::getenv("GM2_DW9_AT");
+    const unsigned scope = fence && std::string(fence) == "system" ? 0u : (unsigned)hipEventReleaseToDevice;
+    return SchedEnv{hipEventDisableTiming | scope, hold ? std::max(1, std::atoi(hold)) : 3,
+                    at ? std::max(0, std::atoi(at)) : 2, std::getenv("GM2_TAIL_MAIN") != nullptr};
   }();
-  return f;
+  return env;
 }
 
 struct WsState {
@@ -380,8 +394,8 @@ struct WsState {
     HIP_OK(hipGetDevice(&dev));
     HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     for (auto& e : bucket) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&slot_done, order_event_flags()));
-    HIP_OK(hipEventCreateWithFlags(&adam9_done, order_event_flags()));
+    HIP_OK(hipEventCreateWithFlags(&slot_done, sched_env().order_event_flags));
+    HIP_OK(hipEventCreateWithFlags(&adam9_done, sched_env().order_event_flags));
   }
   void destroy() {
     if (side) (void)hipStreamDestroy(side);
@@ -400,7 +414,7 @@ struct WsState {
       HIP_OK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
       if (ev.empty()) {
         ev.resize(64);
-        for (auto& e : ev) HIP_OK(hipEventCreateWithFlags(&e, order_event_flags()));
+        for (auto& e : ev) HIP_OK(hipEventCreateWithFlags(&e, sched_env().order_event_flags));
       }
     }
     return side;
@@ -632,6 +646,23 @@ X3Plan x3_plan(const Ctx<T>& c, int B) {
   return p;
 }
 
+// The plans of one call on B rows, computed once (after the call's input slot or zero-copy operands
+// are set in c: big_grads reads them) and shared by its forward and backward
+template <typename T>
+struct StepPlan {
+  X3Plan xp;
+  BigGrads<T> bg;
+  // this step's backward takes the clip statistics (NormAhead): both big weight gradients in one
+  // pass with the tile sums in their epilogues (the split ones take none)
+  bool norm_ahead;
+};
+template <typename T>
+StepPlan<T> step_plan(const Ctx<T>& c, int B) {  // (host arithmetic only: safe before B is range-checked)
+  StepPlan<T> p{x3_plan<T>(c, B), big_grads<T>(c, (int)round_up(B, kTile)), false};
+  p.norm_ahead = p.bg.direct && !p.xp.dw9 && !p.xp.dwe0;
+  return p;
+}
+
 // Tensor tables. kind 0: the 9 Linear weights with their natural-layout shadow (tile0 counts
 // 64x64 tiles; fp32 -> shadow sync). kind 1: all 30 parameters in reference order, weights with
 // their shadow (tile0 counts 4096-element blocks; fused Adam writes the shadow).
@@ -737,7 +768,7 @@ void bn_apply(const Ctx<T>& c, const BnPass& p, int i) {
   double* syncb = (double*)(c.ws + l.syncb);
   if (p.sync) {  // SyncBN: this rank's column sums -> all-reduce -> the global batch's statistics
     launch_bn_sync_pack(c.f(l.bnpart), p.B, H, 0, syncb, c.s);
-    c.st->allreduce(syncb, 2 * H + 2, c.s);
+    c.st.allreduce(syncb, 2 * H + 2, c.s);
   }
   float* run = p.bn + (int64_t)i * 2 * H;
   launch_bn_fwd_apply<T>(c.f(l.Y[i]), H, c.f(l.bnpart), p.B, p.Bp, H, p.train, p.prm + c.d.off[kBlk[i][2]],
@@ -785,7 +816,7 @@ void encoder_half(const Ctx<T>& c, const gm2_batch* b, const BnPass& p, const X3
   // a queued output-layer Adam update of the previous step starts here, beside the hidden layers
   // (HBM-bound next to latency-bound small GEMMs; the gather and the input-layer GEMM before this
   // point leave it nothing: one is HBM-bound too, the other holds every CU's registers)
-  if (c.st) c.st->kick(c.s);
+  c.st.kick(c.s);
   bn_apply<T>(c, p, 0);
   bn_layer<T>(c, p, 1, c.t(l.A[0]), H, H, H);
   bn_layer<T>(c, p, 2, c.t(l.A[1]), H, H, H);
@@ -831,23 +862,24 @@ struct FwdCall {
 // forward (train or eval). Fills A_l, Y_l, save_l, HD, Z and runs the fused reconstruction-loss
 // epilogue (dL when with_grad), or the probabilities / counts epilogue.
 template <typename T>
-void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, const FwdCall& f) {
+void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, const StepPlan<T>& plan,
+             const FwdCall& f) {
   const Dims& d = c.d;
   const Layout& l = c.lo;
   const int B = (int)b->n;
   if (B <= 0 || B > d.Bm) throw Gm2Error("batch rows %d outside (0, batch_max=%lld]", B, (long long)d.Bm);
-  const bool sync = f.train && c.st && c.st->opt.sync_bn;
+  const bool sync = f.train && c.st.opt.sync_bn;
   // (SyncBN: the batch statistics span every rank's rows, so one row here is fine)
   if (f.train && B < 2 && !sync) throw Gm2Error("Expected more than 1 value per channel when training (batch of 1)");
   check_batch_data(b, d, "batch");
   const int Bp = (int)round_up(B, kTile), H = (int)d.H;
   // 1, 2) strain rows, encoder blocks, heads + reparameterisation, decoder blocks (all NT GEMMs)
-  const X3Plan xp = x3_plan<T>(c, B);
+  const X3Plan& xp = plan.xp;
   const int64_t Gq = l.Gq;
   const BnPass p{prm, bn, B, Bp, f.train, sync, /*save=*/true};
   encoder_half<T>(c, b, p, xp, true, f.staged, f.with_grad != 0);
   decoder_half<T>(c, p);
-  if (c.st) c.st->join(c.s);  // (a deferred output-layer update must be complete before the output layer)
+  c.st.join(c.s);  // (a deferred output-layer update must be complete before the output layer)
   if (f.probs || f.counts) {  // 3') VAE.forward: p = sigmoid(logits) (model.py:89-90) and / or the
                               // per-strain (TP, FP, FN) of (p > thr) vs the strain's genes; no loss
     GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, B, (int)d.G, H, Bp, (int)d.Gp, 0};
@@ -867,12 +899,8 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, c
     launch_gemm_recon_loss<T>(g, prm + d.off[D9B], c.ridx ? c.xbres : (const uint32_t*)(c.ws + c.xbo),
                               c.ridx ? c.ld_xbres : d.Gp / 32, f.with_grad, f.scal, c.t(l.dL), d.Gp,
                               c.f(l.losspart), c.f(l.colpart), d.Gp, c.s, c.ridx);
-  int na_ok = 0, na_n = 0;
-  if (f.norm_hdr) {  // the training call: record whether its backward takes the clip statistics
-    const BigGrads<T> bg = big_grads<T>(c, Bp);
-    na_ok = bg.direct && !xp.dw9 && !xp.dwe0 ? 1 : 0;  // (the split weight gradients take no clip statistics)
-    na_n = bg.n9 + bg.n0;
-  }
+  // the training call: record whether its backward takes the clip statistics
+  const int na_ok = f.norm_hdr && plan.norm_ahead ? 1 : 0, na_n = f.norm_hdr ? plan.bg.n9 + plan.bg.n0 : 0;
   // 4) loss slot sums + the output bias's gradient (column sums of dL): nothing in the backward
   // reads them before its final join, so a training call hands the launch to the backward, which
   // puts it on the side stream behind its first fork (off the critical path, one launch and its
@@ -887,9 +915,7 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, c
   auto tail = [=](hipStream_t s) {
     launch_fwd_tail(lpart, nlp, kpart, nkp, loss, cpart, rt, Gp, G, bgrad, hdr, na_ok, na_n, s);
   };
-  // (env GM2_TAIL_MAIN: on the caller's stream, as before; A/B profiles/r03_fwd_tail_side_ab.txt)
-  static const bool tail_main = std::getenv("GM2_TAIL_MAIN") != nullptr;
-  if (f.defer_tail && !tail_main) *f.defer_tail = tail;
+  if (f.defer_tail && !sched_env().tail_main) *f.defer_tail = tail;
   else tail(c.s);
 }
 
@@ -908,232 +934,320 @@ struct BwdCall {
   std::function<void(hipStream_t)>* fwd_tail = nullptr;  // the forward's deferred tail launch
 };
 
-// Backward. Every operand is read in the layout its producer wrote: weight gradients use MN-major P
-// and Q (dW[out][in] = sum_b dY[b][out] * in[b][in]), input gradients an MN-major weight
-// (dX[b][in] = sum_out dY[b][out] * W[out][in]); no transposed copy exists anywhere.
+// ---------------------------------------------------------------------------------------------
+// The backward schedule, in named stages. The caller's stream runs the chain dA5 -> BatchNorm
+// backward -> dX -> ... down to the input layer; weight gradients and bias sums go to a side stream:
+// they are off the critical path and fill the tails of the chain's launches, and the join at the end
+// orders them before the caller's work. Every operand is read in the layout its producer wrote:
+// weight gradients use MN-major P and Q (dW[out][in] = sum_b dY[b][out] * in[b][in]), input gradients
+// an MN-major weight (dX[b][in] = sum_out dY[b][out] * W[out][in]).
+// ---------------------------------------------------------------------------------------------
+// what the stages of one backward share
+template <typename T>
+struct BwdPass {
+  const float* prm;
+  float* gr;
+  int B, Bp, H;
+  int train;    // BatchNorm ran on batch statistics
+  bool sync;    // SyncBN: the batch-coupling sums span every rank's rows
+  Ctx<T> c, w;  // the caller's stream; the side stream with its own split-K scratch (GM2_OPT_SIDE_STREAM = 0: c again)
+  bool sr;      // w is a stream of its own
+  // fork: the side stream waits for everything on the caller's stream so far
+  void fork() const {
+    if (sr) c.st.order(c.s, w.s);
+  }
+  // bias-gradient partials of layer i (6: the heads), each in a slice of its own: summed on the side stream
+  float* col_partials(int i) const { return c.f(c.lo.colbwd) + (int64_t)i * c.lo.colbwd_cap; }
+};
+
+// what a dX GEMM leaves in the caller's stream's slab area for BatchNorm j's backward: S split-K slabs
+// of `slab` elements; have_part: the GEMM's epilogue took BatchNorm j's backward partials already
+struct DxOut {
+  int S;
+  bool have_part;
+  int64_t slab;
+};
+
+// dA_j = dY . W (K-major dY, MN-major W) into the slab area, on the caller's stream; when the plan
+// allows, the epilogue also takes BatchNorm j's backward partials (sum do, sum (y-mean) do). The
+// mirror of linear_pre_bn.
+template <typename T>
+DxOut dx_pre_bn(const BwdPass<T>& p, const T* dY, int64_t lddy, const T* W, int64_t ldw, int K, int j) {
+  const Ctx<T>& c = p.c;
+  const Layout& l = c.lo;
+  const int H = p.H;
+  GemmArgs<T> g{dY, lddy, W, ldw, p.B, H, K, p.Bp, H, 0, 1, 0};
+  StoreEpi bn;
+  bn.mode = 2, bn.part = (float2*)c.f(l.bnpart), bn.ldp = H, bn.Y = c.f(l.Y[j]), bn.ldy = H, bn.H = H;
+  bn.save = c.f(l.save[j]), bn.gamma = p.prm + c.d.off[kBlk[j][2]], bn.beta = p.prm + c.d.off[kBlk[j][3]];
+  const bool part = launch_gemm_bn<T>(g, c.f(c.slab_off), H, nullptr, bn, c.s);
+  return {part ? 1 : gemm_to_slabs(c, g, H), part, (int64_t)p.Bp * H};
+}
+
+// dA5[b][h] = sum_g dL[b][g] W9[g][h]; bf16x3: dL K-major and W9 MN-major (its natural [G][H] rows
+// interleaved) split on the caller's stream, three products to slabs of Bq rows
+template <typename T>
+DxOut da5(const BwdPass<T>& p, const X3Plan& xp) {
+  const Ctx<T>& c = p.c;
+  const Layout& l = c.lo;
+  const int H = p.H, G = (int)c.d.G, Gp = (int)c.d.Gp, Gq = (int)l.Gq;
+  if (!xp.da5) return dx_pre_bn<T>(p, c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
+  launch_split_kmajor(c.f(l.dL), Gp, p.B, G, xp.Bq, Gq, c.h(l.x3dlk), 2 * (int64_t)Gq, 0, nullptr, 0, c.s);
+  launch_split_rows(c.f(l.sD3), H, G, H, Gq, H, c.h(l.x3w9m), H, c.s);
+  return {gemm_to_slabs(c, xp.g_da5, H, true), false, (int64_t)xp.Bq * H};
+}
+
+// BatchNorm + ReLU backward of layer i, on the caller's stream: the partial kernel when dA_i's
+// epilogue did not take the partials (it also sums split-K slabs into DA), the SyncBN pack and
+// all-reduce, then the apply: dA_i -> dY_i, the BatchNorm parameter gradients, the bias partials.
+// The mirror of bn_apply.
+template <typename T>
+void bn_bwd(const BwdPass<T>& p, int i, const DxOut& dx) {
+  const Ctx<T>& c = p.c;
+  const Layout& l = c.lo;
+  const int H = p.H;
+  const int64_t og = c.d.off[kBlk[i][2]], ob = c.d.off[kBlk[i][3]];  // gamma, beta
+  float* dA = dx.S > 1 ? c.f(l.DA) : nullptr;
+  if (!dx.have_part)
+    launch_bn_bwd_partial(c.f(c.slab_off), dx.S, dx.slab, c.f(l.Y[i]), H, c.f(l.save[i]), p.prm + og, p.prm + ob, p.B,
+                          H, c.f(l.bnpart), dA, c.s);
+  double* syncb = p.sync ? (double*)(c.ws + l.syncb) : nullptr;
+  if (p.sync) {  // SyncBN: the batch-coupling sums of the backward over every rank's rows
+    launch_bn_sync_pack(c.f(l.bnpart), p.B, H, 1, syncb, c.s);
+    c.st.allreduce(syncb, 2 * H + 2, c.s);
+  }
+  // (input layer, bf16: its only consumer is dWe0, which reads dY0 transposed -- written that way
+  // by the same pass instead of through a transpose launch)
+  T* dYT = i == 0 && sizeof(T) == 2 ? c.t(l.dYT0) : nullptr;
+  launch_bn_bwd_apply<T>(dA ? dA : c.f(c.slab_off), c.f(l.Y[i]), H, c.f(l.bnpart), p.B, p.Bp, H, p.train,
+                         c.f(l.save[i]), p.prm + og, p.prm + ob, p.gr + og, p.gr + ob, c.t(l.dY[i]), p.col_partials(i),
+                         c.s, syncb, dYT, p.Bp);
+}
+
+// Side stream, item i of the chain. Layer i: its bias gradient (column sum of the apply's partials)
+// and weight gradient dW_i = dY_i^T . in_i (layer 3: in = Z; the input layer's own is
+// input_weight_grad). kHeadsItem: the head biases' column sum, then the MUW | LVW gradient from dH.
+constexpr int kHeadsItem = 6;
+template <typename T>
+void side_layer(const BwdPass<T>& p, int i) {
+  const Ctx<T>& w = p.w;
+  const Layout& l = w.lo;
+  const Dims& d = w.d;
+  const int H = p.H, Bp = p.Bp, L = (int)d.L, Lr = (int)d.Lr, L2r = (int)d.L2r;
+  float* gr = p.gr;
+  if (i == kHeadsItem) {
+    launch_colsum(p.col_partials(i), Bp / kReparamRows, 2 * L, 2 * L, gr + d.off[MUB], gr + d.off[LVB], L, w.s);
+    gemm_to(w, GemmArgs<T>{w.t(l.dH), L2r, w.t(l.A[2]), H, 2 * L, H, Bp, L2r, H, 0, 0, 0}, gr + d.off[MUW],
+            gr + d.off[LVW], L, H);
+    return;
+  }
+  launch_colsum(p.col_partials(i), Bp / 64, H, H, gr + d.off[kBlk[i][1]], nullptr, 0, w.s);
+  if (i == 0) return;
+  const T* dY = w.t(l.dY[i]);
+  float* dW = gr + d.off[kBlk[i][0]];
+  if (i == 3) gemm_to(w, GemmArgs<T>{dY, H, w.t(l.Z), Lr, H, L, Bp, H, Lr, 0, 0, 0}, dW, nullptr, 0, L);
+  else gemm_to(w, GemmArgs<T>{dY, H, w.t(l.A[i - 1]), H, H, H, Bp, H, H, 0, 0, 0}, dW, nullptr, 0, H);
+}
+
+// The fork point of side item `id` (in chain order: 5, 4, 3, the heads, 2, 1, 0): the side stream
+// waits for the chain so far, then takes the items held back before and this one. `hold`
+// (GM2_FORK_HOLD, SchedEnv): no fork here, the item waits for the next fork taken. Without a side
+// stream nothing is held.
+struct HeldItems {
+  int id[7], n = 0;
+};
+template <typename T>
+void fork_side(const BwdPass<T>& p, HeldItems& held, bool hold, int id) {
+  if (hold && p.sr) {
+    held.id[held.n++] = id;
+    return;
+  }
+  p.fork();
+  for (int k = 0; k < held.n; ++k) side_layer<T>(p, held.id[k]);
+  held.n = 0;
+  side_layer<T>(p, id);
+}
+
+// Latent bottleneck, on the caller's stream: dZ = dY3 . W_D0 to slabs, then back through the
+// reparameterisation: dH = d(mu | logvar) (with the KL terms of scal and any external dmu / dlogvar)
+// and the head biases' partials
+template <typename T>
+void latent_dx(const BwdPass<T>& p, const float* eps, const float* scal, const BwdCall& bw) {
+  const Ctx<T>& c = p.c;
+  const Layout& l = c.lo;
+  const int H = p.H, L = (int)c.d.L, Lr = (int)c.d.Lr;
+  const int S = gemm_to_slabs(c, GemmArgs<T>{c.t(l.dY[3]), H, c.t(l.sD0), Lr, p.B, L, H, p.Bp, Lr, 0, 1, 0}, L);
+  launch_reparam_bwd<T>(c.f(c.slab_off), S, (int64_t)p.Bp * L, L, c.f(l.HD), eps, scal, p.B, p.Bp, L, c.t(l.dH),
+                        (int)c.d.L2r, bw.dmu_ext, bw.dlv_ext, p.col_partials(kHeadsItem), c.s);
+}
+
+// Output-layer weight gradient (gradient bucket 0), on the side stream behind a fork of its own, the
+// forward's deferred tail (loss slot sums, output bias gradient, norm-ahead header) right in front
+// of it: dW9[g][h] = sum_b dL[b][g] A5[b][h], written as dW9^T[h][g] = sum_b A5^T[h][b] dL[b][g]
+// with A5^T K-major (a transposed copy made here) and dL MN-major, stored transposed: one
+// transposed-read operand instead of two (the 256x256 tile is LDS-read bound with two). Plans with
+// split-K keep the both-MN-major form.
+// Its place is behind the GM2_DW9_AT-th kernel of the caller's stream's chain (0 = dA5, 1 = layer 5's
+// BatchNorm backward apply, 2 = the first hidden dX GEMM, ...). Alongside dA5 it would take the CUs
+// dA5 needs; after it, its 860 tiles start as the hidden chain's first kernels do (the chain's head
+// start is the gap the position leaves), and the tail runs on CUs dA5 no longer holds (right after
+// the first fork it starved beside dA5 for ~360 us and held dW9 back,
+// profiles/r04_fwd_tail_after_dw9.txt). Default 2 with dW9 on its capped grid (GM2_OPT_GRID_CAP bit 1,
+// 215 workgroups x 4 tiles): the chain's BatchNorm partial and apply run before dW9 takes 215 CUs,
+// and 41 CUs stay with the chain -- 6 of 6 same-box pairs faster than 0 on the full grid
+// (profiles/r05_dw9_cap_ab.txt). (Last instead, beside dWe0, measured the same step time on one GPU;
+// first keeps gradient bucket 0 early for the data-parallel exchange.)
+template <typename T>
+void output_weight_grad(const BwdPass<T>& p, const StepPlan<T>& plan, std::function<void(hipStream_t)>* fwd_tail) {
+  const Ctx<T>&c = p.c, &w = p.w;
+  const Layout& l = c.lo;
+  const int H = p.H, G = (int)c.d.G, Gp = (int)c.d.Gp, Gq = (int)l.Gq;
+  const X3Plan& xp = plan.xp;
+  float* dW9 = p.gr + c.d.off[D9W];
+  p.fork();
+  if (fwd_tail && *fwd_tail) {
+    (*fwd_tail)(w.s);
+    *fwd_tail = nullptr;
+  }
+  if (xp.dw9) {  // bf16x3: dL and A5 as MN-major splits (k = the batch row), both made on this stream
+    launch_split_rows(c.f(l.dL), Gp, p.B, G, xp.Bq, Gq, c.h(l.x3dlm), Gq, w.s);
+    launch_split_rows(c.f(l.A[5]), H, p.B, H, xp.Bq, H, c.h(l.x3a5m), H, w.s);
+    gemm_to(w, xp.g_dw9, dW9, nullptr, 0, H, true);
+  } else if (plan_gemm<T>(plan.bg.g9).splits == 1) {
+    // (A5^T here on the side stream; on the main stream before the fork measured ~35 us/step
+    // slower, profiles/r02_a5t_placement_ab.txt)
+    launch_transpose<T>(c.t(l.A[5]), H, p.Bp, H, c.t(l.AT5), p.Bp, w.s);
+    launch_gemm_trans<T>(plan.bg.g9, dW9, H, w.s, plan.bg.direct ? (double*)(c.ws + l.nasq) : nullptr);
+  } else {
+    gemm_to(w, GemmArgs<T>{c.t(l.dL), Gp, c.t(l.A[5]), H, G, H, p.Bp, Gp, H, 0, 0, 0}, dW9, nullptr, 0, H);
+  }
+  if (c.st.opt.grad_buckets) HIP_OK(hipEventRecord(c.st.bucket[0], w.s));
+}
+
+// Quarter q of the input-layer weight gradient (gradient bucket 2 + q) is final on `s`; `rest`: so
+// are the quarters after it (one launch wrote them all), which share its event
+void input_quarters_final(WsState& st, hipStream_t s, int q, bool rest) {
+  if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2 + q], s));
+  for (int k = q; k < (rest ? 4 : q + 1); ++k) st.bucket_ev[2 + k] = 2 + q;
+}
+
+// Input-layer weight gradient, on the caller's stream (nothing is left to overlap):
+// dWe0[h][g] = sum_b dY0^T[h][b] X[b][g], dY0^T a K-major copy (bf16: bn_bwd wrote it), X MN-major.
+// Gradient bucket 1 (every hidden-layer tensor) is final when the side stream's queue so far is; dWe0
+// starts without waiting for it (the join follows the dWe0 launch: the side stream's last small GEMM
+// and column sums run beside dWe0's first tiles instead of before them).
+template <typename T>
+void input_weight_grad(const BwdPass<T>& p, const StepPlan<T>& plan) {
+  const Ctx<T>& c = p.c;
+  const Layout& l = c.lo;
+  WsState& st = c.st;
+  const int H = p.H, G = (int)c.d.G;
+  const X3Plan& xp = plan.xp;
+  const BigGrads<T>& bg = plan.bg;
+  float* dW0 = p.gr + c.d.off[E0W];
+  if (sizeof(T) != 2 && !xp.dwe0) launch_transpose<T>(c.t(l.dY[0]), H, p.Bp, H, c.t(l.dYT0), p.Bp, c.s);
+  if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[1], p.w.s));
+  if (!xp.dwe0 && input_chunked(bg, H)) {  // four row-quarter launches, bucket 2 + q final after launch q
+    for (int q = 0; q < 4; ++q) {
+      GemmArgs<T> gq = bg.g0;
+      const int r0 = (int)input_quarter_row(c.d, q);
+      gq.P = bg.g0.P + (int64_t)r0 * bg.g0.ldp;
+      gq.M = gq.Mp = H / 4;
+      if (!launch_gemm_sq<T>(gq, dW0 + (int64_t)r0 * G, G, nullptr, c.s, true))
+        throw Gm2Error("input-layer quarter GEMM: not a one-pass plan");
+      input_quarters_final(st, c.s, q, false);
+    }
+    return;
+  }
+  if (xp.dwe0) {  // bf16x3: dY0 as an MN-major split, X's rows (exact in bf16) named twice by the row table
+    launch_split_rows(c.f(l.dY[0]), H, p.B, H, xp.Bq, H, c.h(l.x3dy0), H, c.s);
+    launch_dup_rows((int32_t*)(c.ws + l.x3rows), 2 * xp.Bq, c.s);
+    gemm_to(c, xp.g_dwe0, dW0, nullptr, 0, G, true);
+  } else if (!bg.direct || !launch_gemm_sq<T>(bg.g0, dW0, G, (double*)(c.ws + l.nasq) + bg.n9, c.s, false)) {
+    gemm_to(c, bg.g0, dW0, nullptr, 0, G);
+  }
+  input_quarters_final(st, c.s, 0, true);  // one GEMM: buckets 2..5 become final together
+}
+
+// The next batch's rows -> the other input slot (gm2_batch.next), on the side stream behind a fork
+// placed after dWe0 (beside it, the gather only slows the GEMM down by its own length; that slot's
+// readers, the previous step, are earlier): under the data-parallel exchange of the input-layer
+// gradient, or beside the clip / Adam passes on one GPU. Joined back before the call returns: the
+// caller's stream orders every write this call makes (workspace lifetime; no device-wide sync is
+// needed); the clip / Adam passes that follow wait for it, which measured time-neutral (both are
+// HBM-bound) and keeps the gather beside the exchange, which waits on bucket events instead.
+template <typename T>
+void stage_next(const BwdPass<T>& p, const NextStage& nx) {
+  const Ctx<T>& c = p.c;
+  const int G = (int)c.d.G, Gp = (int)c.d.Gp, Bn = (int)nx.b->n;
+  p.fork();
+  launch_gather_rows<T>(nx.b->data, nx.b->ld_data, nx.b->rows, Bn, G, c.t(nx.xo), Gp, Gp, (int)round_up(Bn, kTile),
+                        (uint32_t*)(c.ws + nx.xbo), Gp / 32, p.w.s);
+  HIP_OK(hipEventRecord(nx.done, p.w.s));
+  if (p.sr) c.st.order(p.w.s, c.s);
+}
+
+// Backward of the fused loss (or of outside output gradients, gm2_backward_outputs): the stages
+// above in launch order
 template <typename T>
 void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, const float* scal,
-              const BwdCall& bw) {
-  const NextStage* nx = bw.next;
-  const Dims& d = c.d;
+              const StepPlan<T>& plan, const BwdCall& bw) {
   const Layout& l = c.lo;
-  const int B = (int)b->n, Bp = (int)round_up(B, kTile);
-  const int H = (int)d.H, L = (int)d.L, G = (int)d.G;
-  const int Gp = (int)d.Gp, Lr = (int)d.Lr, L2r = (int)d.L2r;
-  // weight gradients go to a side stream: they are off the critical path (dY -> dX -> BN -> ...)
-  // and fill the tails of its launches; the join at the end orders them before the caller's work
-  WsState& st = *c.st;
+  WsState& st = c.st;
+  const SchedEnv& env = sched_env();
   const hipStream_t side = st.side_stream();
-  const bool sr = side != nullptr;
-  const Ctx<T> w = sr ? c.side(side) : c;
-  auto fork = [&] {
-    if (sr) st.order(c.s, w.s);
-  };
-  // The side-stream work of the first hidden layers (5, 4, 3 and the heads) would queue behind dW9
-  // on the side stream anyway: it is enqueued at the fork of layer 2 instead, one ordering event in
-  // place of five (each costs the main stream ~7 us; -7..-11 us per step, profiles/r03_fork_batch_ab.txt;
-  // holding layer 2 as well measured +15 us). Env GM2_FORK_HOLD = the first layer whose own fork is
-  // taken (6 = every layer forks), for A/Bs.
-  static const int hold_from = [] {
-    const char* e = std::getenv("GM2_FORK_HOLD");
-    return e ? std::max(1, std::atoi(e)) : 3;
-  }();
-  std::vector<std::function<void()>> held;
-  auto side_work = [&](bool hold, std::function<void()> f) {
-    if (hold && sr) {
-      held.push_back(std::move(f));
-      return;
-    }
-    f();
-  };
-  auto fork_flush = [&](bool hold) {
-    if (hold && sr) return;
-    fork();
-    for (auto& f : held) f();
-    held.clear();
-  };
-  // output layer: dW9[g][h] = sum_b dL[b][g] A5[b][h] ; dA5[b][h] = sum_g dL[b][g] W9[g][h]
-  // (its bias gradient was summed in the forward's recon epilogue, before the fork)
-  // Written as dW9^T[h][g] = sum_b A5^T[h][b] dL[b][g] with A5^T K-major (a transposed copy made
-  // here) and dL MN-major, stored transposed: one transposed-read operand instead of two (the
-  // 256x256 tile is LDS-read bound with two). Plans with split-K keep the both-MN-major form.
-  // (Forking it last instead, beside the input-layer dWe0 GEMM, measured the same step time on one
-  // GPU; first keeps gradient bucket 0 early for the data-parallel exchange.)
-  const BigGrads<T> bg = big_grads<T>(c, Bp);
-  const X3Plan xp = x3_plan<T>(c, B);
-  const int Gq = (int)l.Gq;
-  double* nasq = (double*)(c.ws + l.nasq);
-  // the forward's deferred tail launch (loss sums, output bias gradient): behind the first fork
-  auto tail_on = [&](hipStream_t s) {
-    if (bw.fwd_tail && *bw.fwd_tail) {
-      (*bw.fwd_tail)(s);
-      *bw.fwd_tail = nullptr;
-    }
-  };
-  // The output-layer weight gradient (dW9, gradient bucket 0) is ordered on the side stream behind
-  // an explicit point of the main stream's chain: its `dw9_at`-th kernel counted from dA5 (0 = dA5,
-  // 1 = layer 5's BatchNorm backward apply, 2 = the first hidden dX GEMM, ...; env GM2_DW9_AT for
-  // A/Bs). Launched alongside dA5 it would take the CUs dA5 needs; after dA5 its 860 tiles start as
-  // the hidden chain's first kernels do (the chain's head start is the gap dw9_at leaves). The
-  // forward tail (loss slot sums, output bias gradient, norm-ahead header) runs right in front of
-  // it, on CUs dA5 no longer holds. (Rounds 3-4 had the tail in front of dW9 right after the first
-  // fork: starved beside dA5 for ~360 us, it was what held dW9 back; profiles/r04_fwd_tail_after_dw9.txt.)
-  // Default 2 with dW9 on its capped grid (GM2_OPT_GRID_CAP bit 1, 215 workgroups x 4 tiles): the
-  // chain's BatchNorm partial and apply run before dW9 takes 215 CUs, and 41 CUs stay with the
-  // chain -- 6 of 6 same-box pairs faster than 0 on the full grid (profiles/r05_dw9_cap_ab.txt).
-  static const int dw9_at = [] {
-    const char* e = std::getenv("GM2_DW9_AT");
-    return e ? std::max(0, std::atoi(e)) : 2;
-  }();
-  const hipStream_t s9 = sr ? w.s : c.s;
-  bool dw9_done = false;
-  auto dw9_launch = [&] {
-    if (dw9_done) return;
-    dw9_done = true;
-    const GemmArgs<T>& g9 = bg.g9;
-    const bool direct9 = plan_gemm<T>(g9).splits == 1;
-    fork();
-    tail_on(s9);
-    if (xp.dw9) {  // bf16x3: dL and A5 as MN-major splits (k = the batch row), both made on this stream
-      launch_split_rows(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlm), Gq, s9);
-      launch_split_rows(c.f(l.A[5]), H, B, H, xp.Bq, H, c.h(l.x3a5m), H, s9);
-      gemm_to(w, xp.g_dw9, gr + d.off[D9W], nullptr, 0, H, true);
-    } else if (direct9) {
-      // (A5^T here on the side stream; on the main stream before the fork measured ~35 us/step
-      // slower, profiles/r02_a5t_placement_ab.txt)
-      launch_transpose<T>(c.t(l.A[5]), H, Bp, H, c.t(l.AT5), Bp, s9);
-      launch_gemm_trans<T>(g9, gr + d.off[D9W], H, s9, bg.direct ? nasq : nullptr);
-    } else {
-      gemm_to(w, GemmArgs<T>{c.t(l.dL), Gp, c.t(l.A[5]), H, G, H, Bp, Gp, H, 0, 0, 0}, gr + d.off[D9W], nullptr, 0, H);
-    }
-    if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[0], s9));
-  };
+  const int B = (int)b->n, H = (int)c.d.H;
+  const BwdPass<T> p{prm, gr, B, (int)round_up(B, kTile), H, bw.train, bw.train && st.opt.sync_bn,
+                     c, side ? c.side(side) : c, side != nullptr};
+  HeldItems held;
+  const auto hold = [&](int i) { return i >= env.fork_hold; };
+  // dW9 goes behind kernel env.dw9_at of the chain: mark() follows each of them (dA5, then every
+  // BatchNorm apply and dX GEMM in turn)
   int chain_pos = 0;
-  auto chain_mark = [&] {  // after each kernel of the main stream's chain
-    if (chain_pos++ == dw9_at) dw9_launch();
+  bool dw9_done = false;
+  const auto mark = [&] {
+    if (chain_pos++ != env.dw9_at) return;
+    output_weight_grad<T>(p, plan, bw.fwd_tail);
+    dw9_done = true;
   };
-  // dA_j = dY . W (K-major dY, MN-major W) into the slab area; when the plan allows, the GEMM's
-  // epilogue also takes BatchNorm j's backward partials (sum do, sum (y-mean) do)
-  bool have_part = false;
-  auto dx_pre_bn = [&](const T* dY, int64_t lddy, const T* W, int64_t ldw, int K, int j) {
-    GemmArgs<T> g{dY, lddy, W, ldw, B, H, K, Bp, H, 0, 1, 0};
-    StoreEpi bn;
-    bn.mode = 2, bn.part = (float2*)c.f(l.bnpart), bn.ldp = H, bn.Y = c.f(l.Y[j]), bn.ldy = H, bn.H = H;
-    bn.save = c.f(l.save[j]), bn.gamma = prm + d.off[kBlk[j][2]], bn.beta = prm + d.off[kBlk[j][3]];
-    have_part = launch_gemm_bn<T>(g, c.f(c.slab_off), H, nullptr, bn, c.s);
-    return have_part ? 1 : gemm_to_slabs(c, g, H);
-  };
-  int S;
-  if (xp.da5) {  // bf16x3: dL K-major and W9 MN-major (its natural [G][H] rows interleaved), to slabs
-    launch_split_kmajor(c.f(l.dL), Gp, B, G, xp.Bq, Gq, c.h(l.x3dlk), 2 * (int64_t)Gq, 0, nullptr, 0, c.s);
-    launch_split_rows(c.f(l.sD3), H, G, H, Gq, H, c.h(l.x3w9m), H, c.s);
-    S = gemm_to_slabs(c, xp.g_da5, H, true);
-  } else {
-    S = dx_pre_bn(c.t(l.dL), Gp, c.t(l.sD3), H, Gp, 5);
+  // 1) output layer's input gradient
+  DxOut dx = da5<T>(p, plan.xp);
+  mark();
+  // 2) layers 5, 4: BatchNorm backward, the fork (or hold) of the layer's side work, dX
+  for (int i : {5, 4}) {
+    bn_bwd<T>(p, i, dx);
+    mark();
+    fork_side<T>(p, held, hold(i), i);
+    dx = dx_pre_bn<T>(p, c.t(l.dY[i]), H, c.t(l.shadow(i)), H, H, i - 1);
+    mark();
   }
-  chain_mark();
-  for (int i = 5; i >= 0; --i) {
-    const int64_t slab = (int64_t)(i == 5 && xp.da5 ? xp.Bq : Bp) * H;
-    const bool sum = S > 1;
-    if (!have_part)
-      launch_bn_bwd_partial(c.f(c.slab_off), S, slab, c.f(l.Y[i]), H, c.f(l.save[i]), prm + d.off[kBlk[i][2]],
-                            prm + d.off[kBlk[i][3]], B, H, c.f(l.bnpart), sum ? c.f(l.DA) : nullptr, c.s);
-    // bias-gradient partials go to this layer's own slice: their column sum runs on the side stream
-    float* colp = c.f(l.colbwd) + (int64_t)i * l.colbwd_cap;
-    const bool sync = bw.train && st.opt.sync_bn;
-    double* syncb = (double*)(c.ws + l.syncb);
-    if (sync) {  // SyncBN: the batch-coupling sums of the backward over every rank's rows
-      launch_bn_sync_pack(c.f(l.bnpart), B, H, 1, syncb, c.s);
-      st.allreduce(syncb, 2 * H + 2, c.s);
-    }
-    // (input layer, bf16: its only consumer is dWe0, which reads dY0 transposed -- written that way
-    // by the same pass instead of through a transpose launch)
-    const bool dyt = i == 0 && sizeof(T) == 2;
-    launch_bn_bwd_apply<T>(sum ? c.f(l.DA) : c.f(c.slab_off), c.f(l.Y[i]), H, c.f(l.bnpart), B, Bp, H, bw.train,
-                           c.f(l.save[i]), prm + d.off[kBlk[i][2]], prm + d.off[kBlk[i][3]], gr + d.off[kBlk[i][2]],
-                           gr + d.off[kBlk[i][3]], c.t(l.dY[i]), colp, c.s, sync ? syncb : nullptr,
-                           dyt ? c.t(l.dYT0) : nullptr, Bp);
-    chain_mark();
-    const bool hold = i >= hold_from;
-    fork_flush(hold);
-    side_work(hold, [&, colp, i] { launch_colsum(colp, Bp / 64, H, H, gr + d.off[kBlk[i][1]], nullptr, 0, w.s); });
-    const T* dY = c.t(l.dY[i]);
-    if (i == 0) {  // input layer: weight gradient only (on the main stream: nothing left to overlap)
-      dw9_launch();  // (a dw9_at past the chain's end: here, beside dWe0)
-      // dWe0[h][g] = sum_b dY0^T[h][b] X[b][g]: dY0^T (K-major copy) x X (MN-major)
-      if (!dyt && !xp.dwe0) launch_transpose<T>(dY, H, Bp, H, c.t(l.dYT0), Bp, c.s);
-      // bucket 1 (every hidden-layer weight gradient) is final when the side stream's queue so far
-      // is; dWe0 starts without waiting for it (the join follows the dWe0 launch: the side stream's
-      // last small GEMM / column sums run beside dWe0's first tiles instead of before them)
-      if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[1], w.s));
-      if (xp.dwe0) {  // bf16x3: dY0 as an MN-major split, X's rows (exact in bf16) named twice by the row table
-        launch_split_rows(c.f(l.dY[0]), H, B, H, xp.Bq, H, c.h(l.x3dy0), H, c.s);
-        launch_dup_rows((int32_t*)(c.ws + l.x3rows), 2 * xp.Bq, c.s);
-        gemm_to(c, xp.g_dwe0, gr + d.off[E0W], nullptr, 0, G, true);
-        if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2], c.s));
-        for (int q = 0; q < 4; ++q) st.bucket_ev[2 + q] = 2;
-      } else if (input_chunked(bg, H)) {  // four row-quarter launches, bucket 2 + q final after launch q
-        for (int q = 0; q < 4; ++q) {
-          GemmArgs<T> gq = bg.g0;
-          const int r0 = (int)input_quarter_row(d, q);
-          gq.P = bg.g0.P + (int64_t)r0 * bg.g0.ldp;
-          gq.M = gq.Mp = H / 4;
-          if (!launch_gemm_sq<T>(gq, gr + d.off[E0W] + (int64_t)r0 * G, G, nullptr, c.s, true))
-            throw Gm2Error("input-layer quarter GEMM: not a one-pass plan");
-          if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2 + q], c.s));
-          st.bucket_ev[2 + q] = 2 + q;
-        }
-      } else {
-        if (!bg.direct || !launch_gemm_sq<T>(bg.g0, gr + d.off[E0W], G, nasq + bg.n9, c.s, false))
-          gemm_to(c, bg.g0, gr + d.off[E0W], nullptr, 0, G);
-        // one launch: buckets 2..5 become final together, one event marks all four
-        if (st.opt.grad_buckets) HIP_OK(hipEventRecord(st.bucket[2], c.s));
-        for (int q = 0; q < 4; ++q) st.bucket_ev[2 + q] = 2;
-      }
-      if (sr) st.order(w.s, c.s);  // join: the caller's stream sees every weight gradient
-      if (nx) {  // the next batch's rows -> the other input slot, on the side stream after dWe0 (beside
-                 // it, it only slows the GEMM down by its own length): under the data-parallel exchange
-                 // of the input-layer gradient, or beside the clip / Adam passes on one GPU
-        const hipStream_t gs = sr ? w.s : c.s;
-        if (sr) st.order(c.s, w.s);  // placed after dWe0 (that slot's readers, the previous step, are earlier)
-        const int Bn = (int)nx->b->n;
-        launch_gather_rows<T>(nx->b->data, nx->b->ld_data, nx->b->rows, Bn, G, c.t(nx->xo), Gp, Gp,
-                              (int)round_up(Bn, kTile), (uint32_t*)(c.ws + nx->xbo), Gp / 32, gs);
-        HIP_OK(hipEventRecord(nx->done, gs));
-        // joined back before the call returns: the caller's stream orders every write this call
-        // makes (workspace lifetime, device-wide syncs are not needed); the clip / Adam passes that
-        // follow wait for it, which measured time-neutral (both are HBM-bound) and keeps the gather
-        // beside the data-parallel exchange, which waits on bucket events instead
-        if (sr) st.order(w.s, c.s);
-      }
-      st.recorded = st.opt.grad_buckets != 0;
-      break;
-    }
-    if (i == 3) {  // decoder input layer, then back through the reparameterisation and the heads
-      side_work(3 >= hold_from, [&, dY] {
-        gemm_to(w, GemmArgs<T>{dY, H, c.t(l.Z), Lr, H, L, Bp, H, Lr, 0, 0, 0}, gr + d.off[D0W], nullptr, 0, L);
-      });
-      S = gemm_to_slabs(c, GemmArgs<T>{dY, H, c.t(l.sD0), Lr, B, L, H, Bp, Lr, 0, 1, 0}, L);
-      float* colh = c.f(l.colbwd) + 6 * l.colbwd_cap;
-      launch_reparam_bwd<T>(c.f(c.slab_off), S, (int64_t)Bp * L, L, c.f(l.HD), b->eps, scal, B, Bp, L, c.t(l.dH),
-                            L2r, bw.dmu_ext, bw.dlv_ext, colh, c.s);
-      fork_flush(3 >= hold_from);
-      side_work(3 >= hold_from, [&, colh] {
-        launch_colsum(colh, Bp / kReparamRows, 2 * L, 2 * L, gr + d.off[MUB], gr + d.off[LVB], L, w.s);
-        gemm_to(w, GemmArgs<T>{c.t(l.dH), L2r, c.t(l.A[2]), H, 2 * L, H, Bp, L2r, H, 0, 0, 0}, gr + d.off[MUW],
-                gr + d.off[LVW], L, H);
-      });
-      S = dx_pre_bn(c.t(l.dH), L2r, c.t(l.sHD), H, (int)d.K2L, 2);
-      chain_mark();
-      continue;
-    }
-    side_work(hold, [&, dY, i] {
-      gemm_to(w, GemmArgs<T>{dY, H, c.t(l.A[i - 1]), H, H, H, Bp, H, H, 0, 0, 0}, gr + d.off[kBlk[i][0]], nullptr, 0,
-              H);
-    });
-    S = dx_pre_bn(dY, H, c.t(l.shadow(i)), H, H, i - 1);
-    chain_mark();
+  // 3) latent bottleneck: layer 3, back through the reparameterisation, the heads
+  bn_bwd<T>(p, 3, dx);
+  mark();
+  fork_side<T>(p, held, hold(3), 3);
+  latent_dx<T>(p, b->eps, scal, bw);
+  fork_side<T>(p, held, hold(3), kHeadsItem);
+  dx = dx_pre_bn<T>(p, c.t(l.dH), c.d.L2r, c.t(l.sHD), H, (int)c.d.K2L, 2);
+  mark();
+  // 4) layers 2, 1
+  for (int i : {2, 1}) {
+    bn_bwd<T>(p, i, dx);
+    mark();
+    fork_side<T>(p, held, hold(i), i);
+    dx = dx_pre_bn<T>(p, c.t(l.dY[i]), H, c.t(l.shadow(i)), H, H, i - 1);
+    mark();
   }
+  // 5) input layer: its fork is always taken, and whatever was held goes with it
+  bn_bwd<T>(p, 0, dx);
+  mark();
+  fork_side<T>(p, held, false, 0);
+  if (!dw9_done) output_weight_grad<T>(p, plan, bw.fwd_tail);  // (GM2_DW9_AT past the chain's end: beside dWe0)
+  input_weight_grad<T>(p, plan);
+  // 6) join: the caller's stream sees every weight gradient
+  if (p.sr) st.order(p.w.s, c.s);
+  // 7) the next batch's gather
+  if (bw.next) stage_next<T>(p, *bw.next);
+  st.recorded = st.opt.grad_buckets != 0;
 }
 
 // The sampling decode's output layer, gated per tile (extras.py:196-201, decode + threshold).
@@ -1197,10 +1311,8 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   bf16_t* w1 = (bf16_t*)(c.ws + l.s3w1);
   launch_split3(c.f(l.A[5]), H, n, Bq, H, a3, 2 * H, rn, ablk, c.s, single ? a1 : nullptr);
   launch_split3(w9, H, G, Gq, H, w3, 2 * H, cn, wblk, c.s, single ? w1 : nullptr);
-  if (c.st) {
-    c.st->decode_cum = (const unsigned long long*)(ctl + DecodeCtl::kCum);
-    c.st->decode_ovf = (const unsigned long long*)(c.ws + l.s3ovf);
-  }
+  c.st.decode_cum = (const unsigned long long*)(ctl + DecodeCtl::kCum);
+  c.st.decode_ovf = (const unsigned long long*)(c.ws + l.s3ovf);
   // band half-widths per unit ||a_r|| ||w_g|| (MaskBand): single tiles carry the operands' bf16
   // rounding and the fp32 accumulation of their H products, split tiles the split's own error and the
   // fp32 accumulation of its 3H products, exact tiles the fp32 accumulation of H products; all, the
@@ -1267,7 +1379,7 @@ void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, const Dec
   if constexpr (std::is_same_v<T, float>) {
     if (!o.probs && opts().sample_split && decode_split3(c, prm, n, o.mask, o.ldm, o.bits, o.ldb)) return;
   }
-  if (c.st) c.st->exact_decodes++;
+  c.st.exact_decodes++;
   GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, n, (int)d.G, H, Bp, (int)d.Gp, 0};
   launch_gemm_mask<T>(g, prm + d.off[D9B], o.mask, o.ldm, o.probs, o.ldpr, c.s, o.bits, o.ldb);
 }
@@ -1331,13 +1443,8 @@ void run_train(const Layout& lo, const gm2_batch* b, const float* prm, float* gr
     sync_bn_no_rows(lo, gr, bn, loss, ws, (hipStream_t)strm, st);
     return;
   }
-  Ctx<T> c(lo, ws, strm, &st);
+  Ctx<T> c(lo, ws, strm, st);
   c.x3 = lo.x3 && st.opt.train_split != 0;
-  if (lo.x3) {  // GM2_TSTAT_*: this call's five G-wide GEMMs
-    const int n = x3_plan<T>(c, (int)b->n).count();
-    st.x3_split += n;
-    st.x3_exact += 5 - n;
-  }
   SlotState& ss = st.slot;
   bool hit = false;
   int slot = 0;
@@ -1364,14 +1471,20 @@ void run_train(const Layout& lo, const gm2_batch* b, const float* prm, float* gr
     nx.b = nb, nx.done = st.slot_done;
     nx.xo = slot ? lo.X : lo.X1, nx.xbo = slot ? lo.XB : lo.XB1;
   }
+  const StepPlan<T> plan = step_plan<T>(c, (int)b->n);
+  if (lo.x3) {  // GM2_TSTAT_*: this call's five G-wide GEMMs
+    const int n = plan.xp.count();
+    st.x3_split += n;
+    st.x3_exact += 5 - n;
+  }
   std::function<void(hipStream_t)> tail;
   FwdCall fw;
   fw.train = fw.with_grad = 1, fw.scal = scal, fw.loss = loss, fw.grads = gr;
   fw.norm_hdr = true, fw.staged = hit, fw.defer_tail = &tail;
-  forward<T>(c, b, prm, bn, fw);
+  forward<T>(c, b, prm, bn, plan, fw);
   BwdCall bw;
   bw.next = nb ? &nx : nullptr, bw.fwd_tail = &tail;
-  backward<T>(c, b, prm, gr, scal, bw);
+  backward<T>(c, b, prm, gr, scal, plan, bw);
   if (nb) {
     ss.staged = true, ss.slot = slot ^ 1;
     ss.data = nb->data, ss.ld = nb->ld_data, ss.rows = nb->rows, ss.n = nb->n;
@@ -1410,7 +1523,7 @@ int decode_rows(const gm2_dims* d, const float* params, const float* bn_running,
     const bool ld_short = packed ? o.ldb < gm2_packed_row_bytes(lo.d.G) : o.ldm < lo.d.G;
     if (ld_short || (o.probs && o.ldpr < lo.d.G))
       throw Gm2Error(packed ? "decode_bits: ld too small" : "decode: ld < G");
-    Ctx<float> c(lo, ws, stream, &st);
+    Ctx<float> c(lo, ws, stream, st);
     // z [n][L] -> Z [Bm][Lp] (pad columns stay zero from workspace init)
     HIP_OK(hipMemcpy2DAsync(c.f(lo.Z), lo.d.Lr * 4, z, lo.d.L * 4, lo.d.L * 4, n, hipMemcpyDeviceToDevice, c.s));
     decode_chain<float>(c, params, const_cast<float*>(bn_running), (int)n, o);
@@ -1455,7 +1568,7 @@ int gm2_sync_shadows(const gm2_dims* d, int prec, const float* params, void* ws,
     const Layout lo = make_layout(d, prec);
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       launch_shadow_sync<T>(make_table(c), params, c.s);
     });
   });
@@ -1528,7 +1641,7 @@ int gm2_adam_step(const gm2_dims* d, int prec, float* params, const float* grads
     const float* clip = (const float*)((char*)ws + lo.clip);
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       const TensorTable all = make_table(c, 1);
       if (!st.opt.defer_adam || !st.opt.side_stream) {
         launch_adam_fused<T>(all, grads, params, m, v, scalars, clip, c.s);
@@ -1554,16 +1667,17 @@ int gm2_eval_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const 
     float* bn = const_cast<float*>(bn_running);  // eval mode never writes running stats
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       c.x3 = lo.x3 && st.opt.train_split != 0;  // (x3_plan: f32 elements only)
+      const StepPlan<T> plan = step_plan<T>(c, (int)batch->n);
       if (lo.x3) {  // GM2_TSTAT_*: the input layer and the output layer + loss
-        const X3Plan xp = x3_plan<T>(c, (int)batch->n);
+        const X3Plan& xp = plan.xp;
         st.x3_split += (int)xp.enc0 + (int)xp.loss;
         st.x3_exact += 2 - ((int)xp.enc0 + (int)xp.loss);
       }
       FwdCall fw;
       fw.scal = scalars, fw.loss = loss;
-      forward<T>(c, batch, params, bn, fw);
+      forward<T>(c, batch, params, bn, plan, fw);
     });
   });
 }
@@ -1843,10 +1957,10 @@ int gm2_recon_counts(const gm2_dims* d, int prec, const gm2_batch* batch, const 
     float* bn = const_cast<float*>(bn_running);  // eval mode never writes running stats
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       FwdCall fw;
       fw.counts = counts, fw.thr = threshold;
-      forward<T>(c, batch, params, bn, fw);
+      forward<T>(c, batch, params, bn, step_plan<T>(c, (int)batch->n), fw);
     });
   });
 }
@@ -1860,7 +1974,7 @@ int gm2_encode(const gm2_dims* d, int prec, const gm2_batch* batch, const float*
     b.eps = nullptr;  // (mu and logvar alone: no z is drawn)
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       const int B = (int)b.n;
       if (B <= 0 || B > c.d.Bm) throw Gm2Error("encode rows outside (0, batch_max]");
       check_batch_data(&b, c.d, "encode");
@@ -1920,10 +2034,10 @@ int gm2_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const float
     if (!batch->eps) throw Gm2Error("forward: eps required (model.py:102 draws it)");
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       FwdCall fw;
       fw.train = train, fw.probs = probs, fw.ld_probs = ld_probs;
-      forward<T>(c, batch, params, bn_running, fw);
+      forward<T>(c, batch, params, bn_running, step_plan<T>(c, (int)batch->n), fw);
       copy_heads<T>(c, batch->n, mu, logvar);
     });
   });
@@ -1938,7 +2052,7 @@ int gm2_backward_outputs(const gm2_dims* d, int prec, const gm2_batch* batch, co
     if (!probs || !dprobs || ld_probs < lo.d.G) throw Gm2Error("backward_outputs: probs / dprobs required");
     by_precision(lo.prec, [&](auto tag) {
       using T = decltype(tag);
-      Ctx<T> c(lo, ws, stream, &st);
+      Ctx<T> c(lo, ws, stream, st);
       const Dims& dd = c.d;
       const int B = (int)batch->n, Bp = (int)round_up(B, kTile);
       if (B <= 0 || B > dd.Bm) throw Gm2Error("backward_outputs: rows outside (0, batch_max]");
@@ -1950,7 +2064,7 @@ int gm2_backward_outputs(const gm2_dims* d, int prec, const gm2_batch* batch, co
       HIP_OK(hipMemsetAsync(scal0, 0, GM2_NUM_SCALARS * 4, c.s));
       BwdCall bw;
       bw.dmu_ext = dmu, bw.dlv_ext = dlogvar, bw.train = train;
-      backward<T>(c, batch, params, grads, scal0, bw);
+      backward<T>(c, batch, params, grads, scal0, step_plan<T>(c, B), bw);
     });
   });
 }
