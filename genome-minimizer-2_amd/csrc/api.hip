@@ -1,5 +1,5 @@
 // C-ABI of libgm2 (include/gm2.h): workspace layout + the per-step kernel schedule of the VAE
-// train / eval / sample hot path. Host-side only; kernels live in gemm.hip and kernels.hip.
+// train / eval / sample hot path. Host-side only; kernels live in gemm_*.hip and kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -148,6 +148,33 @@ struct Layout {
   int64_t Gq = 0, Bq = 0;
   int64_t x3w0, x3w9k, x3w9m, x3xd, x3x, x3a5k, x3a5m, x3dlk, x3dlm, x3dy0, x3rows;
 };
+
+// the control block (DecodeCtl) and the overflow area (Layout::s3ovf) of workspace `ws` by name, for a
+// decode over Bq x Gq padded rows x genes (multiples of 256)
+DecodeCounters decode_counters(char* ws, const Layout& l, int Bq, int Gq) {
+  unsigned* ctl = (unsigned*)(ws + l.s3ctl);
+  unsigned* ovf = (unsigned*)(ws + l.s3ovf);
+  const int tiles = (Bq / 256) * (Gq / 256);
+  DecodeCounters k;
+  k.cum = (unsigned long long*)(ctl + DecodeCtl::kCum);
+  k.ovf_cum = (unsigned long long*)ovf;
+  k.tiles_split = ctl + DecodeCtl::kTilesSplit;
+  k.tiles_exact = ctl + DecodeCtl::kTilesExact;
+  k.tiles_single = ctl + DecodeCtl::kTilesSingle;
+  k.shard_counts = ctl + DecodeCtl::kCounts;
+  k.flips = ctl + DecodeCtl::kFlips;
+  k.tile_found = ctl + DecodeCtl::kTileFound;
+  k.ablk = ctl + DecodeCtl::kBlk;
+  k.wblk = k.ablk + Bq / 256;
+  k.ovf_count = ovf + Layout::kOvfCount;
+  k.ovf_flags = ovf + Layout::kOvfFlags;
+  k.ovf_list = k.ovf_flags + tiles;
+  k.ctl_zero = k.tiles_split;
+  k.ctl_zero_bytes = (size_t)(DecodeCtl::kBlk - DecodeCtl::kTilesSplit + Bq / 256 + Gq / 256) * 4;
+  k.ovf_zero = k.ovf_count;
+  k.ovf_zero_bytes = (size_t)(Layout::kOvfFlags - Layout::kOvfCount + tiles) * 4;
+  return k;
+}
 
 #ifdef GM2_DEBUG
 // (offset, bytes) of every region the last make_layout on this thread took (gm2_debug_check_layout)
@@ -883,8 +910,11 @@ void forward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* bn, c
   if (f.probs || f.counts) {  // 3') VAE.forward: p = sigmoid(logits) (model.py:89-90) and / or the
                               // per-strain (TP, FP, FN) of (p > thr) vs the strain's genes; no loss
     GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, B, (int)d.G, H, Bp, (int)d.Gp, 0};
-    launch_gemm_mask<T>(g, prm + d.off[D9B], nullptr, 0, f.probs, f.ld_probs, c.s, nullptr, 0, f.counts,
-                        (const uint32_t*)(c.ws + c.xbo), d.Gp / 32, f.thr);
+    MaskOut o;
+    o.probs = f.probs, o.ldpr = f.ld_probs;
+    o.counts = f.counts, o.xbits = (const uint32_t*)(c.ws + c.xbo), o.ldxb = d.Gp / 32;
+    o.thr = f.thr;
+    launch_gemm_mask<T>(g, prm + d.off[D9B], o, false, c.s);
     return;
   }
   // 3) output layer + reconstruction loss (+ dlogits), computed as logit^T: genes x strains
@@ -1295,24 +1325,29 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
     bits = (uint8_t*)(c.ws + l.s3bits);
     ldb = l.s3ldb;
   }
-  unsigned* ctl = (unsigned*)(c.ws + l.s3ctl);
-  unsigned* ablk = ctl + DecodeCtl::kBlk;
-  unsigned* wblk = ablk + Bq / 256;
+  const DecodeCounters k = decode_counters(c.ws, l, Bq, Gq);
   bf16_t* a3 = (bf16_t*)(c.ws + l.s3a);
   bf16_t* w3 = (bf16_t*)(c.ws + l.s3w);
   float* rn = c.f(l.s3rn);
   float* cn = c.f(l.s3cn);
-  uint2* list = (uint2*)(c.ws + l.s3band);
   const float* w9 = prm + d.off[D9W];
-  HIP_OK(hipMemsetAsync(ctl + DecodeCtl::kTilesSplit, 0, (DecodeCtl::kBlk - DecodeCtl::kTilesSplit + Bq / 256 + Gq / 256) * 4,
-                        c.s));
+  HIP_OK(hipMemsetAsync(k.ctl_zero, 0, k.ctl_zero_bytes, c.s));
   const bool single = opts().sample_single != 0 && H % 64 == 0;  // (the single GEMM's K = H: 64-wide K-tiles)
   bf16_t* a1 = (bf16_t*)(c.ws + l.s3a1);
   bf16_t* w1 = (bf16_t*)(c.ws + l.s3w1);
-  launch_split3(c.f(l.A[5]), H, n, Bq, H, a3, 2 * H, rn, ablk, c.s, single ? a1 : nullptr);
-  launch_split3(w9, H, G, Gq, H, w3, 2 * H, cn, wblk, c.s, single ? w1 : nullptr);
-  c.st.decode_cum = (const unsigned long long*)(ctl + DecodeCtl::kCum);
-  c.st.decode_ovf = (const unsigned long long*)(c.ws + l.s3ovf);
+  launch_split3(c.f(l.A[5]), H, n, Bq, H, a3, 2 * H, rn, k.ablk, c.s, single ? a1 : nullptr);
+  launch_split3(w9, H, G, Gq, H, w3, 2 * H, cn, k.wblk, c.s, single ? w1 : nullptr);
+  c.st.decode_cum = k.cum;
+  c.st.decode_ovf = k.ovf_cum;
+  // The three tiers' bands from one base. Entries past a shard's capacity flag their 256 x 256 block,
+  // which k_band_tile_fix then recomputes whole in fp64 (no bit is left as a bf16 tier decided it).
+  const int tiles = (Bq / 256) * (Gq / 256);
+  MaskBand base;
+  base.rn = rn, base.cn = cn;
+  base.counts = k.shard_counts, base.list = (uint2*)(c.ws + l.s3band);
+  base.cap = (unsigned)std::min<int>(opts().band_cap, (int)kBandShardCap);
+  base.oflag = k.ovf_flags, base.olist = k.ovf_list, base.ocount = k.ovf_count;
+  base.obn = Gq / 256, base.oblocks = (unsigned)tiles;
   // band half-widths per unit ||a_r|| ||w_g|| (MaskBand): single tiles carry the operands' bf16
   // rounding and the fp32 accumulation of their H products, split tiles the split's own error and the
   // fp32 accumulation of its 3H products, exact tiles the fp32 accumulation of H products; all, the
@@ -1320,58 +1355,49 @@ bool decode_split3(const Ctx<float>& c, const float* prm, int n, uint8_t* mask, 
   const double gH = band_gamma((double)H), g3H = band_gamma(3.0 * H);
   // (the split and single kernels' tiles keep their band elements in their own slots -- the tile
   // grid is the same and each tile runs in one of them; the exact kernel's, rare, go to the shards)
-  const int tiles = (Bq / 256) * (Gq / 256);
-  MaskBand bs{rn, cn, (float)(kSplitUnit * 1.01 + g3H + gH), ctl + DecodeCtl::kCounts, list, kBandShardCap};
-  MaskBand be = bs;
+  MaskBand be = base;
   be.coef = (float)(2.0 * gH);
+  MaskBand bs = base;
+  bs.coef = (float)(kSplitUnit * 1.01 + g3H + gH);
   bs.tlist = (uint2*)(c.ws + l.s3tlist), bs.tcount = (unsigned*)(c.ws + l.s3tcount);
-  bs.tfound = ctl + DecodeCtl::kTileFound, bs.tslots = kBandTileSlots;
+  bs.tfound = k.tile_found, bs.tslots = kBandTileSlots;
   MaskBand b1 = bs;
-  b1.coef = (float)(kSingleUnit * 1.01 + 2.0 * gH), b1.drop_overflow = 1, b1.tiles_done = ctl + DecodeCtl::kTilesSingle;
+  b1.coef = (float)(kSingleUnit * 1.01 + 2.0 * gH), b1.drop_overflow = 1, b1.tiles_done = k.tiles_single;
   HIP_OK(hipMemsetAsync(bs.tcount, 0, (size_t)tiles * 4, c.s));
-  // band-list overflow: entries past a shard's capacity flag their 256 x 256 block, which
-  // k_band_tile_fix then recomputes whole in fp64 (no bit is left as a bf16 tier decided it)
-  unsigned* ovf = (unsigned*)(c.ws + l.s3ovf);
-  HIP_OK(hipMemsetAsync(ovf + Layout::kOvfCount, 0, (size_t)(Layout::kOvfFlags - Layout::kOvfCount + tiles) * 4, c.s));
-  bs.cap = (unsigned)std::min<int>(opts().band_cap, (int)kBandShardCap);
-  bs.oflag = ovf + Layout::kOvfFlags, bs.olist = bs.oflag + tiles, bs.ocount = ovf + Layout::kOvfCount;
-  bs.obn = Gq / 256, bs.oblocks = (unsigned)tiles;
-  be.cap = bs.cap, be.oflag = bs.oflag, be.olist = bs.olist, be.ocount = bs.ocount;
-  be.obn = bs.obn, be.oblocks = bs.oblocks;
-  const int on = single ? 1 : 0;
-  const double single_bound = opts().single_bound_milli * 1e-3;  // (GM2_OPT_SAMPLE_SINGLE_BOUND, for A/Bs and tests)
+  HIP_OK(hipMemsetAsync(k.ovf_zero, 0, k.ovf_zero_bytes, c.s));
+  // every tier writes the packed bits alone, behind the same gate: only its verdict and counter differ
+  MaskGate gate;
+  gate.ablk = k.ablk, gate.wblk = k.wblk;
+  gate.single = single ? 1 : 0;
+  gate.single_bound = opts().single_bound_milli * 1e-3;  // (GM2_OPT_SAMPLE_SINGLE_BOUND, for A/Bs and tests)
+  auto tier = [&](int run, unsigned* ran, const MaskBand& band) {
+    MaskOut o;
+    o.bits = bits, o.ldb = ldb;
+    o.gate = gate, o.gate.run = run, o.gate.tiles = ran;
+    o.band = band;
+    return o;
+  };
+  const MaskOut split = tier(1, k.tiles_split, bs), exact = tier(2, k.tiles_exact, be);
   GemmArgs<bf16_t> g{a3, 2 * H, w3, 2 * H, n, G, 2 * H, Bq, Gq, 0};
-  const MaskGate gs{ablk, wblk, 1, ctl + DecodeCtl::kTilesSplit, on, single_bound};
   if (single) {  // both bf16 tiers in one launch (a single tile whose band overflows re-runs as split)
     GemmArgs<bf16_t> g1{a1, H, w1, H, n, G, H, Bq, Gq, 0};
-    launch_gemm_mask_tiered(g1, g, prm + d.off[D9B], bits, ldb, c.s,
-                            MaskGate{ablk, wblk, 3, ctl + DecodeCtl::kTilesSingle, on, single_bound}, b1, gs, bs);
+    launch_gemm_mask_tiered(g1, g, prm + d.off[D9B], tier(3, k.tiles_single, b1), split, c.s);
   } else {
-    launch_gemm_mask<bf16_t>(g, prm + d.off[D9B], nullptr, 0, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
-                             true, gs, bs);
+    launch_gemm_mask<bf16_t>(g, prm + d.off[D9B], split, true, c.s);
   }
   GemmArgs<float> ge{c.f(l.A[5]), H, c.f(l.sD3), H, n, G, H, (int)round_up(n, kTile), (int)d.Gp, 0};
-  launch_gemm_mask<float>(ge, prm + d.off[D9B], nullptr, 0, nullptr, 0, c.s, bits, ldb, nullptr, nullptr, 0, 0.5f,
-                          false, MaskGate{ablk, wblk, 2, ctl + DecodeCtl::kTilesExact, on, single_bound}, be);
-  launch_band_fix(bs, tiles, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, bits, ldb, ctl + DecodeCtl::kFlips, c.s);
-  launch_band_tile_fix(bs, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, n, G, bits, ldb, ctl + DecodeCtl::kFlips, c.s);
-  launch_decode_stats(ctl + DecodeCtl::kTilesSplit, ctl + DecodeCtl::kTilesExact, ctl + DecodeCtl::kTilesSingle,
-                      ctl + DecodeCtl::kCounts, ctl + DecodeCtl::kTileFound, ctl + DecodeCtl::kFlips, bs.cap,
-                      (unsigned long long*)(ctl + DecodeCtl::kCum), bs.ocount, (unsigned long long*)ovf, c.s);
+  launch_gemm_mask<float>(ge, prm + d.off[D9B], exact, false, c.s);
+  launch_band_fix(bs, tiles, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, bits, ldb, k.flips, c.s);
+  launch_band_tile_fix(bs, c.f(l.A[5]), H, w9, H, prm + d.off[D9B], H, n, G, bits, ldb, k.flips, c.s);
+  launch_decode_stats(k, bs.cap, c.s);
   if (mask) launch_expand_bits(bits, ldb, n, G, mask, ldm, c.s);
   return true;
 }
 
-// where a sampling decode writes: u8 masks [n][ldm] or packed bits [n][ldb], and / or probabilities
-struct DecodeOut {
-  uint8_t *mask = nullptr, *bits = nullptr;
-  float* probs = nullptr;
-  int64_t ldm = 0, ldb = 0, ldpr = 0;
-};
-
-// Z [n][Lr] (in the workspace) -> the decoder half -> the output layer's masks / probabilities
+// Z [n][Lr] (in the workspace) -> the decoder half -> the output layer's masks / probabilities as `o`
+// names them (u8 masks [n][ldm] or packed bits [n][ldb], and / or probabilities; threshold 0.5)
 template <typename T>
-void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, const DecodeOut& o) {
+void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, const MaskOut& o) {
   const Dims& d = c.d;
   const Layout& l = c.lo;
   const int Bp = (int)round_up(n, kTile), H = (int)d.H;
@@ -1381,7 +1407,7 @@ void decode_chain(const Ctx<T>& c, const float* prm, float* bn, int n, const Dec
   }
   c.st.exact_decodes++;
   GemmArgs<T> g{c.t(l.A[5]), H, c.t(l.sD3), H, n, (int)d.G, H, Bp, (int)d.Gp, 0};
-  launch_gemm_mask<T>(g, prm + d.off[D9B], o.mask, o.ldm, o.probs, o.ldpr, c.s, o.bits, o.ldb);
+  launch_gemm_mask<T>(g, prm + d.off[D9B], o, false, c.s);
 }
 
 // make `s` wait for a pending stage on `ws` and forget it (the caller is about to write slot 0)
@@ -1516,7 +1542,7 @@ int with_ws_joined(void* ws, void* stream, F&& f) {
 // The body of gm2_decode_mask and gm2_decode_bits (`packed`): z [n][L] through the decoder of an
 // f32 workspace
 int decode_rows(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
-                const DecodeOut& o, bool packed, void* ws, void* stream) {
+                const MaskOut& o, bool packed, void* ws, void* stream) {
   return with_ws_joined(ws, stream, [&](WsState& st) {
     const Layout lo = make_layout(d, GM2_F32);
     if (n <= 0 || n > lo.d.Bm) throw Gm2Error("decode rows %lld outside (0, batch_max]", (long long)n);
@@ -1684,7 +1710,7 @@ int gm2_eval_forward(const gm2_dims* d, int prec, const gm2_batch* batch, const 
 
 int gm2_decode_mask(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* mask, int64_t ld_mask, float* probs, int64_t ld_probs, void* ws, void* stream) {
-  DecodeOut o;
+  MaskOut o;
   o.mask = mask, o.ldm = ld_mask, o.probs = probs, o.ldpr = ld_probs;
   return decode_rows(d, params, bn_running, z, n, o, false, ws, stream);
 }
@@ -1941,7 +1967,7 @@ int gm2_search_merge(const gm2_search_state* state_in, const gm2_search_state* s
 
 int gm2_decode_bits(const gm2_dims* d, const float* params, const float* bn_running, const float* z, int64_t n,
                     uint8_t* bits, int64_t ld_bits, float* probs, int64_t ld_probs, void* ws, void* stream) {
-  DecodeOut o;
+  MaskOut o;
   o.bits = bits, o.ldb = ld_bits, o.probs = probs, o.ldpr = ld_probs;
   return decode_rows(d, params, bn_running, z, n, o, true, ws, stream);
 }
@@ -2203,7 +2229,7 @@ int gm2_timing_class(int kernel_class, double* total_ms, int64_t* launches) {
 int gm2_debug_flags(unsigned* flags) {
   return guarded([&] {
     if (!flags) throw Gm2Error("null flags");
-    *flags = dbg_take_kernels() | dbg_take_gemm() | dbg_take_masks() | dbg_take_search();
+    *flags = dbg_take_kernels() | dbg_take_gemm_store() | dbg_take_gemm_recon() | dbg_take_gemm_mask() | dbg_take_masks() | dbg_take_search();
   });
 }
 

@@ -1,4 +1,4 @@
-// Launch geometry of the GEMM path: the host-side rules the launchers (gemm.hip) and their callers
+// Launch geometry of the GEMM path: the host-side rules the launchers (gemm_*.hip) and their callers
 // (api.hip) share, each stated once. Plain C++17: no HIP calls, no options, no device queries, so
 // tools/asan/host_asan.cpp checks every rule against a table of expected values without a GPU.
 #pragma once

@@ -135,8 +135,12 @@ struct TimedLaunch {  // records an event pair around a launch when its class is
   hipStream_t s;
   int cls;
 };
+// per-device caches behind the GEMM launch helpers (gemm_launch.hpp; defined once, in timing.hip):
+// raise a kernel's dynamic-LDS limit to `bytes` once per (device, kernel); the current device's CUs
+void ensure_lds_attr(const void* fn, int bytes);
+int device_cus();
 
-// ---- gemm.hip ----
+// ---- gemm_store.hip, gemm_recon.hip ----
 // Options of the fp32 store epilogue (k_gemm_store): BatchNorm statistics of the stored tile, or
 // a transposed store
 struct StoreEpi {
@@ -213,6 +217,8 @@ bool gemm_recon_x3_ok(const GemmArgs<bf16_t>& g);
 void launch_gemm_recon_loss_x3(const GemmArgs<bf16_t>& g, const float* bias, const uint32_t* xbits, int64_t ldxb,
                                int with_grad, const float* scal, float* dL, int64_t ldd, int gcols, int drows,
                                float* loss_part, float* colpart, int64_t ldcol, hipStream_t s);
+
+// ---- gemm_mask.hip ----
 // The bf16x3 sampling decode's error bound (api.hip decode_split3): per logit at most
 // kSplitUnit * ||a_r||_2 * ||w_g||_2 * 1.01 (Cauchy-Schwarz over the split's per-product error). The
 // gate is per 256 x 256 tile: a tile runs split when kSplitUnit * max_r ||a_r|| * max_g ||w_g|| * 1.01
@@ -296,12 +302,28 @@ struct MaskBand {
   unsigned* tiles_done = nullptr;  // [kSplitShards] tiles completed with drop_overflow (statistics)
 };
 inline double band_gamma(double n) { return n * 0x1p-24 / (1.0 - n * 0x1p-24); }
-// the two bf16 tiers of the gated decode in one launch (gemm.hip k_gemm_mask_tiered): g1 / band1
-// the single product (K = H), g3 / band3 the bf16x3 split (K' = 2H), gate3 the verdicts (run 1) and
-// the split tiles' counter; gate1.tiles unused (band1.tiles_done counts the single tiles)
-void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias, uint8_t* bits,
-                             int64_t ldb, hipStream_t s, MaskGate gate1, MaskBand band1, MaskGate gate3,
-                             MaskBand band3);
+// What a mask launch writes (each output optional) and how it decides: pred = sigmoid_fp32(logit) >
+// thr (gemm_mask.hip epilogue 3). The mask kernels take it by value.
+struct MaskOut {
+  uint8_t* mask = nullptr;  // u8 [m][ldm], 0 / 1
+  int64_t ldm = 0;
+  uint8_t* bits = nullptr;  // [m][ldb] bytes, numpy packbits(bitorder='little') rows
+  int64_t ldb = 0;
+  float* probs = nullptr;   // fp32 [m][ldpr]
+  int64_t ldpr = 0;
+  int* counts = nullptr;    // int32 [m][3] += (TP, FP, FN) against the row-major target bits xbits
+  const uint32_t* xbits = nullptr;
+  int64_t ldxb = 0;
+  float thr = 0.5f;
+  MaskGate gate;
+  MaskBand band;
+};
+// the two bf16 tiers of the gated decode in one launch (k_gemm_mask_tiered): g1 / single the single
+// product (K = H), g3 / split the bf16x3 split (K' = 2H). Both write the same packed bits and nothing
+// else; split.gate holds the verdicts (run 1) and the split tiles' counter, single.gate.tiles is
+// unused (single.band.tiles_done counts the single tiles)
+void launch_gemm_mask_tiered(const GemmArgs<bf16_t>& g1, const GemmArgs<bf16_t>& g3, const float* bias,
+                             const MaskOut& single, const MaskOut& split, hipStream_t s);
 // k_band_fix over every shard's entries and every tile's slots: fp64 logit of (A[row], W[gene]) +
 // bias, mask bit = (float)logit > T (the correctly rounded fp32 logit against the reference's
 // threshold) in the packed bits. flips: the bits it changed
@@ -314,22 +336,42 @@ void launch_band_fix(const MaskBand& band, int ntiles, const float* A, int64_t l
 void launch_band_tile_fix(const MaskBand& band, const float* A, int64_t lda, const float* W, int64_t ldw,
                           const float* bias, int H, int n, int G, uint8_t* bits, int64_t ldb, unsigned* flips,
                           hipStream_t s);
-// one workgroup: the decode call's per-call counters -> the workspace's cumulative ones (DecodeCtl);
-// ocount / ocum: the blocks k_band_tile_fix recomputed this call -> their cumulative count
 // packed mask bits [n][ldb] (bit g % 8 of byte g / 8) -> u8 [n][ldm] (0 / 1), any row alignment
 void launch_expand_bits(const uint8_t* bits, int64_t ldb, int n, int G, uint8_t* out, int64_t ldm, hipStream_t s);
-void launch_decode_stats(const unsigned* tiles_split, const unsigned* tiles_exact, const unsigned* tiles_single,
-                         const unsigned* counts, const unsigned* tfound, const unsigned* flips, unsigned cap,
-                         unsigned long long* cum, const unsigned* ocount, unsigned long long* ocum, hipStream_t s);
+// The gated decode's device counters by name: the workspace's control words and overflow area
+// (api.hip decode_ctl builds it; the word offsets live there). Everything but the cumulative
+// counters is per decode call.
+struct DecodeCounters {
+  unsigned long long* cum = nullptr;      // [GM2_STAT_* order] cumulative over the workspace's decodes
+  unsigned long long* ovf_cum = nullptr;  // cumulative blocks k_band_tile_fix recomputed
+  unsigned* tiles_split = nullptr;        // [kSplitShards] tiles each tier ran (MaskGate::tiles;
+  unsigned* tiles_exact = nullptr;        //   single: MaskBand::tiles_done)
+  unsigned* tiles_single = nullptr;
+  unsigned* shard_counts = nullptr;       // [kBandShards] MaskBand::counts
+  unsigned* flips = nullptr;              // bits the fp64 recomputes changed
+  unsigned* tile_found = nullptr;         // [kBandShards] MaskBand::tfound
+  unsigned* ablk = nullptr;               // [Bq / 256] block maxima of ||a_r|| (MaskGate::ablk)
+  unsigned* wblk = nullptr;               // [Gq / 256] block maxima of ||w_g||
+  unsigned* ovf_count = nullptr;          // MaskBand::ocount, oflag [tiles], olist [tiles]
+  unsigned* ovf_flags = nullptr;
+  unsigned* ovf_list = nullptr;
+  // the two spans zeroed per decode: the control words from tiles_split through both block-maxima
+  // arrays, and the overflow area from its count through the flags (the list needs no zeroing)
+  unsigned* ctl_zero = nullptr;
+  size_t ctl_zero_bytes = 0;
+  unsigned* ovf_zero = nullptr;
+  size_t ovf_zero_bytes = 0;
+};
+// one workgroup: the decode call's per-call counters -> the workspace's cumulative ones; cap = the
+// shard capacity the call's bands used
+void launch_decode_stats(const DecodeCounters& k, unsigned cap, hipStream_t s);
 
-// output layer + threshold (sampling / metrics): u8 mask, packed bits, probs, per-row (TP, FP, FN).
-// big (bf16 only): the bf16x3 split decode -- 256x256 ping-pong tiles over operands in
-// launch_split3's interleaved (hi | lo) layout, K = 2 x the hidden width, hi.hi + hi.lo + lo.hi
+// output layer + threshold (sampling / metrics): u8 mask, packed bits, probs, per-row (TP, FP, FN),
+// as `o` names them. big (bf16, packed bits at threshold 0.5 only): the bf16x3 split decode --
+// 256x256 ping-pong tiles over operands in launch_split3's interleaved (hi | lo) layout, K = 2 x the
+// hidden width, hi.hi + hi.lo + lo.hi
 template <typename T>
-void launch_gemm_mask(const GemmArgs<T>& g, const float* bias, uint8_t* mask, int64_t ldm, float* probs,
-                      int64_t ldpr, hipStream_t s, uint8_t* bits = nullptr, int64_t ldb = 0, int* counts = nullptr,
-                      const uint32_t* xbits = nullptr, int64_t ldxb = 0, float thr = 0.5f, bool big = false,
-                      MaskGate gate = {}, MaskBand band = {});
+void launch_gemm_mask(const GemmArgs<T>& g, const float* bias, const MaskOut& o, bool big, hipStream_t s);
 
 // ---- kernels.hip ----
 constexpr int kBnRowChunk = 128;  // rows per BatchNorm partial-statistics chunk
@@ -519,7 +561,9 @@ int grad_stats_blocks(int64_t n);
 #ifdef GM2_DEBUG
 // read-and-clear the debug flag word of each translation unit (gm2_common.hpp DebugBit)
 unsigned dbg_take_kernels();
-unsigned dbg_take_gemm();
+unsigned dbg_take_gemm_store();
+unsigned dbg_take_gemm_recon();
+unsigned dbg_take_gemm_mask();
 unsigned dbg_take_masks();
 unsigned dbg_take_search();
 #endif

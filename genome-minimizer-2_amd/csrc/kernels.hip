@@ -1,7 +1,7 @@
 // Non-GEMM kernels of the VAE hot path: strain-row gather, BatchNorm (train/eval, fwd/bwd),
 // reparameterization + KL, deterministic reductions, clip-norm statistics, Adam, GEMM shadows.
 // All are HBM/latency-bound streaming kernels over [B,H]-sized (or P-sized) data; they keep
-// every padded element of their outputs at zero (the GEMM operand contract, gemm.hip).
+// every padded element of their outputs at zero (the GEMM operand contract, gemm_core.hpp).
 #include "bn_common.hpp"
 #include "gm2_common.hpp"
 #include "gm2_kernels.hpp"
@@ -1771,12 +1771,10 @@ void launch_expand_bits(const uint8_t* bits, int64_t ldb, int n, int G, uint8_t*
   GM2_CHECK_LAUNCH();
 }
 
-void launch_decode_stats(const unsigned* tiles_split, const unsigned* tiles_exact, const unsigned* tiles_single,
-                         const unsigned* counts, const unsigned* tfound, const unsigned* flips, unsigned cap,
-                         unsigned long long* cum, const unsigned* ocount, unsigned long long* ocum, hipStream_t s) {
+void launch_decode_stats(const DecodeCounters& k, unsigned cap, hipStream_t s) {
   static_assert(kSplitShards <= 64 && kBandShards <= 64, "one wave");
-  hipLaunchKernelGGL(k_decode_stats, dim3(1), dim3(64), 0, s, tiles_split, tiles_exact, tiles_single, counts, tfound, flips, cap,
-                     cum, ocount, ocum);
+  hipLaunchKernelGGL(k_decode_stats, dim3(1), dim3(64), 0, s, k.tiles_split, k.tiles_exact, k.tiles_single,
+                     k.shard_counts, k.tile_found, k.flips, cap, k.cum, k.ovf_count, k.ovf_cum);
   GM2_CHECK_LAUNCH();
 }
 

@@ -406,7 +406,7 @@ def test_band_overflow_recomputed_whole_blocks(single, G, N):
     ~2.5e-14 and every gene's bias is the threshold T itself (0x33C00000): each logit is T + delta with
     |delta| of a few fp32 ulps of T (ulp 2^-47), far inside every tier's band (its 2^-20 T floor).
       * single tier on: every tile's band overflows its 256 slots, so each re-runs as bf16x3 in place
-        (counted as split, ADVICE r5 gemm.hip:1408), whose band spills to the shard lists;
+        (counted as split, ADVICE r5, gemm_mask.hip k_gemm_mask_tiered), whose band spills to the shard lists;
       * with the default shard capacity (64 x 65,536) k_band_fix recomputes every element; with
         GM2_OPT_SAMPLE_BAND_CAP = 64 the shards overflow and EVERY tile is recomputed whole in fp64
         by k_band_tile_fix (GM2_STAT_OVERFLOW_TILES);
@@ -539,3 +539,46 @@ def test_odd_latent_width_decodes_on_the_exact_path():
     np.testing.assert_array_equal(np.unpackbits(pm.bits.cpu().numpy(), axis=1, count=G, bitorder="little"),
                                   mask.cpu().numpy())
     assert _masks_ok(mask.cpu().numpy(), P, S, z) == 0
+
+
+def test_decode_paths_agree_bit_for_bit_at_ragged_blocks():
+    """The sampling decode's three output-layer paths -- default (single-product tier + bf16x3),
+    GM2_OPT_SAMPLE_SINGLE = 0 (bf16x3 alone) and GM2_OPT_SAMPLE_SPLIT = 0 (exact fp32) -- at G = 517,
+    n = 300: two 256-row blocks by three 256-gene blocks, ragged in both, H = 128 (a multiple of 64,
+    so the single tier is admitted). Per setting the u8 rows of gm2_decode_mask equal the unpacked
+    rows of gm2_decode_bits in every bit with the pad bits zero, and the counter deltas name the path
+    that ran: the 6 blocks of a gated decode each ran as one single, split or exact tile; with the
+    split off each call is one exact decode. The three settings' masks agree outside the fp64 band."""
+    G, H, L, N = 517, 128, 8, 300
+    P, S = perturb_bn(*oracle_state(G, H, L, 60), seed=61)
+    P["decoder.9.bias"] = torch.linspace(-1.0, 0.8, G)
+    m = to_model(P, S, G, H, L, native.GM2_F32)
+    m.eval()
+    z = torch.randn(N, L, generator=torch.Generator().manual_seed(62))
+    ws = m.workspace(native.GM2_F32, N)
+    out = {}
+    for split, single in ((1, 1), (1, 0), (0, 1)):
+        ws.set_option(native.OPT_SAMPLE_SPLIT, split)
+        ws.set_option(native.OPT_SAMPLE_SINGLE, single)
+        before = m.decode_stats()
+        pm, _ = m.decode_bits(z)
+        mask, _ = m.decode_mask(z)
+        d = _delta(before, m.decode_stats())
+        print(f"split {split} single {single}: {d}")
+        unpacked = np.unpackbits(pm.bits.cpu().numpy(), axis=1, bitorder="little")
+        np.testing.assert_array_equal(unpacked[:, :G], mask.cpu().numpy())
+        assert not unpacked[:, G:].any()
+        if split:  # two gated decodes of 2 x 3 blocks
+            assert d["single_tiles"] + d["split_tiles"] + d["exact_tiles"] == 2 * 6, d
+            assert (d["split_decodes"], d["exact_decodes"]) == (2, 0), d
+            assert (d["single_tiles"] > 0) if single else (d["single_tiles"] == 0), d
+        else:
+            assert (d["split_decodes"], d["exact_decodes"]) == (0, 2), d
+            assert d["single_tiles"] + d["split_tiles"] + d["exact_tiles"] == 0, d
+        out[split, single] = unpacked[:, :G].astype(bool)
+        assert _masks_ok(out[split, single], P, S, z) == 0
+    ws.set_option(native.OPT_SAMPLE_SPLIT, 1)
+    ws.set_option(native.OPT_SAMPLE_SINGLE, 1)
+    band = np.abs(O.decode_logits64(P, S, z).numpy()) <= 1e-3
+    for key in ((1, 0), (0, 1)):
+        assert not ((out[1, 1] != out[key]) & ~band).any()

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill table from hipcc's `-Rpass-analysis=kernel-resource-usage` remarks.
 
-    hipcc ... -Rpass-analysis=kernel-resource-usage -c gemm.hip 2> remarks.txt
+    for u in gemm_store gemm_recon gemm_mask; do
+      hipcc ... -Rpass-analysis=kernel-resource-usage -c $u.hip 2>> remarks.txt
+    done
     python3 tools/kres.py remarks.txt [--grep SUBSTR]
 """
 import re

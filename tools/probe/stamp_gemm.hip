@@ -4,7 +4,8 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DGM2_STAMPS -I../../include
 //        -I../../genome-minimizer-2_amd/csrc stamp_gemm.hip -o stamp_gemm
 // Run:   ./stamp_gemm M N K pk qk      (pk/qk: operand K-major 1 / MN-major 0; random bf16 data)
-#include "../../genome-minimizer-2_amd/csrc/gemm.hip"
+#include "../../genome-minimizer-2_amd/csrc/gemm_store.hip"
+#include "../../genome-minimizer-2_amd/csrc/timing.hip"
 #include "../../genome-minimizer-2_amd/csrc/options.hip"
 
 #include <algorithm>

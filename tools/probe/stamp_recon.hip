@@ -4,7 +4,8 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DGM2_STAMPS -I../../include
 //        -I../../genome-minimizer-2_amd/csrc stamp_recon.hip -o stamp_recon
 // Run:   ./stamp_recon [G B H]      (random bf16 operands, random target bits, v0 scalars)
-#include "../../genome-minimizer-2_amd/csrc/gemm.hip"
+#include "../../genome-minimizer-2_amd/csrc/gemm_recon.hip"
+#include "../../genome-minimizer-2_amd/csrc/timing.hip"
 #include "../../genome-minimizer-2_amd/csrc/options.hip"
 
 #include <algorithm>

@@ -5,7 +5,8 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DGM2_STAMPS] -I../../include
 //        -I../../genome-minimizer-2_amd/csrc time_sq.hip -o time_sq
 // Run:   ./time_sq M N K pk qk mode [reps]
-#include "../../genome-minimizer-2_amd/csrc/gemm.hip"
+#include "../../genome-minimizer-2_amd/csrc/gemm_store.hip"
+#include "../../genome-minimizer-2_amd/csrc/timing.hip"
 #include "../../genome-minimizer-2_amd/csrc/options.hip"
 
 #include <algorithm>
