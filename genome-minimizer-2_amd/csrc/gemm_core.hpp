@@ -309,33 +309,61 @@ constexpr bool kPPDeep = true;
 namespace pp {
 constexpr int REGION = 128 * 128;  // bytes of one half-tile region (128 rows x 128 B, or 64 k x 256 B)
 constexpr int BUF = 4 * REGION;    // one K-tile: A0, A1, B0, B1
+// operand row pitch (elements) up to which a thread's 32-bit source offset holds (stage_half; check_gemm)
+constexpr int64_t kPPMaxLd = int64_t(1) << 24;
 __device__ __forceinline__ int a_row(int r, int a) { return (r >> 6) * 128 + a * 64 + (r & 63); }
 __device__ __forceinline__ int b_row(int r, int b) { return (r >> 5) * 64 + b * 32 + (r & 31); }
 
-// one half-tile: 1024 16-B chunks, 2 per thread (lane-linear LDS destination, swizzled source).
+// element offset from P of 16-B chunk i (0..1023) of half-tile `half` of the tile at (base, k0): the
+// swizzled source of LDS position i (no row table)
+template <bool KMAJ, bool ISA>
+__device__ __forceinline__ int64_t chunk_off(int i, int64_t ld, int base, int half, int k0) {
+  if constexpr (KMAJ) {
+    const int row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);
+    return (int64_t)(base + (ISA ? a_row(row, half) : b_row(row, half))) * ld + k0 + c * 8;
+  } else {
+    const int k = i >> 4, e = ((i & 15) ^ swz_mn(k)) * 8;
+    return (int64_t)(k0 + k) * ld + base + (ISA ? a_row(e, half) : b_row(e, half));
+  }
+}
+
+// one half-tile: 1024 16-B chunks, 2 per thread (lane-linear LDS destination, swizzled source);
+// wave0 = the wave's first thread, wave-uniform.
+// Without a row table chunk_off is a sum of a part that depends on the thread alone and a part that
+// is the same for the whole block: chunk i = j*512 + tid has row (k-row) j*64 + (tid>>3) (j*32 +
+// (tid>>4)); a_row / b_row send j*64 rows to j*128 and a half to +64 / +32 whatever the thread's
+// bits are, and neither swizzle reads the bits j sets. So a load's address is a block-uniform base
+// (tile, half, j, K-tile: scalar arithmetic) plus ONE loop-invariant 32-bit byte offset per thread and
+// operand, and the one 64-bit add of the two is all the vector address arithmetic a load has left.
+// Formed per chunk from chunk_off the main loop spent 34 (both K-major) to 65 (MN-major Q: a 64-bit
+// (k0 + k) * ld per load) VALU instructions per wave and K-tile beside its 64 MFMAs, and held seven
+// 64-bit pointers per thread; now 16 to 21 (profiles/r07_mn_major_b_ab.txt). The offset is below
+// 128 rows * ld * 2 B + 256, so it fits for ld < kPPMaxLd (check_gemm).
 // IDX (zero-copy rows): the thread's two rows (K-major) / k-rows (MN-major), j = 0, 1, are rr[j],
 // read from the tile's LDS index table ahead of the issuing phase (idx_rows below)
 template <bool KMAJ, bool ISA, bool IDX = false>
 __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ P, int64_t ld, int base, int half, int k0,
-                                           char* region, int tid, const int* rr = nullptr) {
+                                           char* region, int tid, int wave0, const int* rr = nullptr) {
+  [[maybe_unused]] const uint32_t voff = 2u * (uint32_t)chunk_off<KMAJ, ISA>(tid, ld, 0, 0, 0);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int i = j * 512 + tid;
-    const bf16_t* src;
-    if constexpr (KMAJ) {
-      const int row = i >> 3;
-      const int c = (i & 7) ^ ((row >> 1) & 7);
-      const int g = ISA ? a_row(row, half) : b_row(row, half);
-      const int64_t r = IDX ? (int64_t)rr[j] : (int64_t)(base + g);
-      src = P + r * ld + k0 + c * 8;
-    } else {
-      const int k = i >> 4;
-      const int e = ((i & 15) ^ swz_mn(k)) * 8;
-      const int g = ISA ? a_row(e, half) : b_row(e, half);
-      const int64_t r = IDX ? (int64_t)rr[j] : (int64_t)(k0 + k);
-      src = P + r * ld + base + g;
+    const void* src;
+    if constexpr (!IDX) {
+      src = (const char*)(P + chunk_off<KMAJ, ISA>(j * 512, ld, base, half, k0)) + voff;
+    } else {  // (table entries are >= 0 and ld < kPPMaxLd: one 32 x 32 -> 64-bit multiply per row)
+      const uint64_t r = (uint64_t)(uint32_t)rr[j] * (uint32_t)ld;
+      if constexpr (KMAJ) {
+        const int row = i >> 3;
+        const int c = (i & 7) ^ ((row >> 1) & 7);
+        src = P + r + k0 + c * 8;
+      } else {
+        const int k = i >> 4;
+        const int e = ((i & 15) ^ swz_mn(k)) * 8;
+        src = P + r + base + (ISA ? a_row(e, half) : b_row(e, half));
+      }
     }
-    __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(region + (j * 512 + (tid & ~63)) * 16), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(src, (lds_void*)(region + (j * 512 + wave0) * 16), 16, 0, 0);
   }
 }
 
@@ -370,6 +398,7 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ P, int64_
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   // wave-uniform in an SGPR: the stagger barriers below must be branched around, not exec-masked
   const int wm = __builtin_amdgcn_readfirstlane(wid >> 2), wn = wid & 3;
+  const int wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);
 #pragma unroll
   for (int a = 0; a < 8; ++a)
 #pragma unroll
@@ -391,8 +420,8 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ P, int64_
   auto issue = [&](int t, int h) {
     const int k0 = kbeg + t * 64;
     char* r = region(t, h);
-    if (h == 0 || h == 3) pp::stage_half<AK, true, IDX == 1>(P, ldp, m0, h == 0 ? 0 : 1, k0, r, tid, h == 0 ? ra0 : ra1);
-    else pp::stage_half<BK, false, IDX == 2>(Q, ldq, n0, h == 1 ? 0 : 1, k0, r, tid, rq);
+    if (h == 0 || h == 3) pp::stage_half<AK, true, IDX == 1>(P, ldp, m0, h == 0 ? 0 : 1, k0, r, tid, wave0, h == 0 ? ra0 : ra1);
+    else pp::stage_half<BK, false, IDX == 2>(Q, ldq, n0, h == 1 ? 0 : 1, k0, r, tid, wave0, rq);
   };
   bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
   auto read_a = [&](int t, int a) {

@@ -12,6 +12,8 @@ static void check_gemm(const GemmArgs<T>& g, int tile) {
   if ((g.pk ? g.ldp < g.K : g.ldp < g.Mp) || (g.qk ? g.ldq < g.K : g.ldq < g.Np)) throw Gm2Error("gemm: ld too small");
   if (((uintptr_t)g.P | (uintptr_t)g.Q) & 15) throw Gm2Error("gemm: operands not 16-B aligned");
   if ((g.ldp * sizeof(T)) % 16 || (g.ldq * sizeof(T)) % 16) throw Gm2Error("gemm: ld not 16-B multiple");
+  if (tile == 256 && (g.ldp >= pp::kPPMaxLd || g.ldq >= pp::kPPMaxLd))  // (stage_half's 32-bit thread offsets)
+    throw Gm2Error("gemm: row pitch %lld / %lld beyond the 256x256 tiles' limit", (long long)g.ldp, (long long)g.ldq);
 }
 
 // Main-loop selection for the 256x256 bf16 tiles: the ping-pong loop (default; measured
