@@ -335,7 +335,9 @@ struct Ctx {
 // bucket events and staged input slot. One workspace is used from one host thread at a time.
 //
 //  * side stream for the weight-gradient GEMMs (fork/join through events; capture-safe), created
-//    on first use; GM2_OPT_SIDE_STREAM = 0 keeps everything on the caller's stream.
+//    on first use; GM2_OPT_SIDE_STREAM = 0 keeps everything on the caller's stream: the same
+//    GEMMs with the same split-K counts into the same buffers (the side work keeps its own
+//    scratch, BwdPass::w), without the fork / join events.
 //  * gradient buckets (data-parallel exchange): ranges of the flat gradient buffer in the order the
 //    backward finalises them, each with an event recorded when its last gradient is written
 //    (gm2_grad_bucket_bounds / gm2_wait_grad_bucket)
@@ -980,8 +982,13 @@ struct BwdPass {
   int B, Bp, H;
   int train;    // BatchNorm ran on batch statistics
   bool sync;    // SyncBN: the batch-coupling sums span every rank's rows
-  Ctx<T> c, w;  // the caller's stream; the side stream with its own split-K scratch (GM2_OPT_SIDE_STREAM = 0: c again)
-  bool sr;      // w is a stream of its own
+  // c: the caller's stream, whose slab area carries each dX result to the next BatchNorm backward.
+  // w: the side work's context, with the split-K scratch of its own (Layout::side_slabs, side_cap) on
+  // the side stream; GM2_OPT_SIDE_STREAM = 0: the same scratch and capacity on the caller's stream, so
+  // side work launched while a dX result is still unread (dW9 at an even GM2_DW9_AT) leaves it alone
+  // and every split count is the side stream's.
+  Ctx<T> c, w;
+  bool sr;  // w is a stream of its own
   // fork: the side stream waits for everything on the caller's stream so far
   void fork() const {
     if (sr) c.st.order(c.s, w.s);
@@ -1228,7 +1235,7 @@ void backward(const Ctx<T>& c, const gm2_batch* b, const float* prm, float* gr, 
   const hipStream_t side = st.side_stream();
   const int B = (int)b->n, H = (int)c.d.H;
   const BwdPass<T> p{prm, gr, B, (int)round_up(B, kTile), H, bw.train, bw.train && st.opt.sync_bn,
-                     c, side ? c.side(side) : c, side != nullptr};
+                     c, c.side(side ? side : c.s), side != nullptr};
   HeldItems held;
   const auto hold = [&](int i) { return i >= env.fork_hold; };
   // dW9 goes behind kernel env.dw9_at of the chain: mark() follows each of them (dA5, then every

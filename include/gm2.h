@@ -442,7 +442,8 @@ int gm2_gemm(int precision, int p_kmajor, int q_kmajor, const void* P, int64_t l
  *                       bf16 GEMM tiles (default), 0 = two-stage loop. Process default from env
  *                       GM2_GEMM_PP (0 disables).
  *   GM2_OPT_SIDE_STREAM 1 = weight-gradient GEMMs on the workspace's forked side stream (default),
- *                       0 = all on the caller's stream. Process default from env GM2_SIDE_STREAM.
+ *                       0 = all on the caller's stream: the same GEMMs into the same buffers, the
+ *                       same results bit for bit. Process default from env GM2_SIDE_STREAM.
  *   GM2_OPT_RECON_TILE  output-layer loss GEMM tile: 0 = plan (default), 128 or 256 = force.
  *   GM2_OPT_SMALL_SPLIT split-K factor (1..8) of the chip-filling short-K 128-tile GEMMs (the
  *                       hidden layers).

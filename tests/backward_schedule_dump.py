@@ -4,9 +4,12 @@ loss[:3], at the end the BatchNorm running statistics and the parameters.
 
 Imported by the test for the in-process schedule variants. Run as a script in a child process (the
 schedule's environment knobs GM2_FORK_HOLD / GM2_DW9_AT / GM2_TAIL_MAIN are read once per process,
-and GM2_LIB_PATH selects another build of the library) it runs every shape at default options and
-writes the tensors with torch.save:   python tests/backward_schedule_dump.py OUT.pt [--c2]
---c2 adds the bench's C2 step shape in bf16, f32 and bf16x3 (a same-results check of two builds)."""
+and GM2_LIB_PATH selects another build of the library) it runs every shape, or the shapes named,
+and writes the tensors with torch.save:
+    python tests/backward_schedule_dump.py OUT.pt [--c2] [--side 0|1] [TAG ...]
+--c2 adds the bench's C2 step shape in bf16, f32 and bf16x3 (a same-results check of two builds);
+--side is GM2_OPT_SIDE_STREAM (default 1), every other option at its default."""
+import argparse
 import functools
 import os
 import sys
@@ -29,11 +32,22 @@ from gpu_helpers import oracle_state, perturb_bn, scalars, synth_x, to_model  # 
 #          gradients 2 slices (slabs + k_slab_sum)
 #   bf16a  hidden dX and dA5 2 slices; dY0 written transposed by the BatchNorm apply; dW9 one pass
 #   bf16b  everything one pass; ragged batch (Bp = 384)
+# The c shapes (Bp = 4096: 128 K-tiles in f32, 64 in bf16, nk / 8 caps the slices) are the smallest at
+# which every precision splits dW9, the one side GEMM that can start while a dX result is unread:
+#   f32c   dA5 2 slices; every other dX one pass (partials in the epilogue); dW9 (133,120-float slabs),
+#          the hidden, latent and head weight gradients and dWe0 16 slices each
+#   bf16c  every dX one pass; dW9, the hidden, latent and head weight gradients and dWe0 8 slices each
+#   x3c    the chain and the hidden weight gradients as f32c (dA5 stays exact fp32: its bf16x3 shape is
+#          no 256-tile plan); dW9 and dWe0 as bf16x3 products on 256-tiles (2 Bq = 8192 K-rows), 16
+#          slices each: 2.1 M floats of slabs, the hidden dX result beside them 4096 x 256 = 1.0 M
 SHAPES = {
     "f32a": ("f32", 517, 256, 16, 100),
     "f32b": ("f32", 1100, 512, 32, 500),
     "bf16a": ("bf16", 1100, 1024, 32, 100),
     "bf16b": ("bf16", 517, 256, 16, 300),
+    "f32c": ("f32", 520, 256, 32, 4000),
+    "bf16c": ("bf16", 520, 256, 32, 4000),
+    "x3c": ("bf16x3", 520, 256, 32, 4000),
 }
 C2 = {p + "_c2": (p, 55039, 1024, 64, 4096) for p in ("bf16", "f32", "bf16x3")}
 STEPS = 2
@@ -78,7 +92,12 @@ def run(tag, inp, side=1, buckets=1, with_next=False):
         sc = scalars(beta=0.37, wgamma=0.55, lam=0.01, step=i + 1)
         sc[native.S_NORM_AHEAD] = 1.0
         loss = torch.zeros(native.LOSS_SLOTS, dtype=torch.float64, device="cuda")
+        split0 = ws.stat(native.TRAIN_STATS["split_gemms"])
         native.train_fwd_bwd(ws, batches[i], m.params, grads, m.bn, sc, loss)
+        if pname == "bf16x3":  # (at least dW9 and dWe0 as split products: not the exact-fp32 fallback)
+            split = ws.stat(native.TRAIN_STATS["split_gemms"]) - split0
+            print(f"{tag} side={side} step {i}: {split} split-bf16 GEMMs")
+            assert split >= 2, (tag, i, split)
         if buckets:  # every bucket's event can be waited on
             for b in range(native.GRAD_BUCKETS):
                 native.wait_grad_bucket(ws, b, waiter)
@@ -94,12 +113,18 @@ def run(tag, inp, side=1, buckets=1, with_next=False):
 
 
 def main():
-    tags = list(SHAPES) + (list(C2) if "--c2" in sys.argv[2:] else [])
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("tags", nargs="*", help="shapes to run (default: every entry of SHAPES)")
+    ap.add_argument("--c2", action="store_true")
+    ap.add_argument("--side", type=int, choices=(0, 1), default=1)
+    a = ap.parse_args()
+    tags = (a.tags or list(SHAPES)) + (list(C2) if a.c2 else [])
     out = {}
     for tag in tags:
-        out.update(run(tag, inputs(tag)))
-    torch.save(out, sys.argv[1])
-    print(f"BWDDUMP {len(out)} tensors -> {sys.argv[1]}")
+        out.update(run(tag, inputs(tag), side=a.side))
+    torch.save(out, a.out)
+    print(f"BWDDUMP {len(out)} tensors -> {a.out}")
 
 
 if __name__ == "__main__":

@@ -54,6 +54,40 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+def prebn_bias(name):
+    """A Linear bias in front of a BatchNorm: its true gradient is exactly zero."""
+    parts = name.split(".")
+    return parts[0] in ("encoder", "decoder") and parts[1] in ("0", "3", "6") and parts[2] == "bias"
+
+
+def grad_bar_failures(specs, offsets, grads, exact, ref, floor, bias_tol, label):
+    """The per-tensor gradient bar of the training-step tests (the C2 method, tests/test_gpu_c2.py), on
+    the flat gradient buffer `grads` of a model with `specs` / `offsets`: on the norm-wise relative
+    error against `exact` (the oracle's gradients in fp64),
+        fro(libgm2) <= 3 * fro(reference arithmetic) + floor,
+    `ref` being the same math in the path's own arithmetic; the pre-BatchNorm biases (true gradient
+    zero: rounding noise on both sides) absolutely, |g| <= bias_tol * the largest gradient of their
+    weight. Prints every tensor's figures and returns the lines of those that miss."""
+    fails = []
+    for i, (name, _) in enumerate(specs):
+        got = grads[offsets[i]:offsets[i + 1]].cpu().double().numpy()
+        ex = exact[name].reshape(-1).cpu().double().numpy()
+        if prebn_bias(name):
+            scale = max(float(np.abs(exact[name.replace("bias", "weight")].cpu().numpy()).max()), 1e-12)
+            if np.abs(got).max() > bias_tol * scale:
+                fails.append(f"{name}: |g|max {np.abs(got).max():.3g} vs weight scale {scale:.3g}")
+            continue
+        r = ref[name].reshape(-1).cpu().double().numpy()
+        nrm = max(float(np.linalg.norm(ex)), 1e-30)
+        f_gpu = float(np.linalg.norm(got - ex)) / nrm
+        f_ref = float(np.linalg.norm(r - ex)) / nrm
+        msg = f"{name}: libgm2 {label} vs exact fro {f_gpu:.3g}; reference arithmetic fro {f_ref:.3g}"
+        print(msg)
+        if not f_gpu <= 3 * f_ref + floor:
+            fails.append(msg)
+    return fails
+
+
 def scalars(beta=0.5, wgamma=0.0, lam=0.0, lr=1e-3, step=1, max_norm=1.0, b1=0.9, b2=0.999, eps=1e-8):
     v = np.zeros(native.NUM_SCALARS)
     v[native.S_BETA], v[native.S_WGAMMA], v[native.S_LAMBDA] = beta, wgamma, lam

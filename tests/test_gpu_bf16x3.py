@@ -12,7 +12,9 @@ five gene-wide GEMMs of a training / evaluation call, which run as split-bf16 pr
      B so the zero pads of hi and lo matter along M / N and K), held to the GM2_F32 bars of
      test_gpu_c2.py: per tensor fro(libgm2) <= 3 fro(torch fp32 oracle) + 2e-4 against the fp64
      oracle, losses [0], [1] rel 1e-5, [2] 1e-4 |.| + 1e-2, clip norm rel 1e-4, sum |theta| rel 1e-6,
-     pre-BN biases absolutely, Adam abs 2e-7; GM2_TSTAT_SPLIT_GEMMS advances by exactly 5.
+     pre-BN biases absolutely, Adam abs 2e-7; GM2_TSTAT_SPLIT_GEMMS advances by exactly 5. The same
+     step with GM2_OPT_SIDE_STREAM = 0 (dW9 shrinks from 8 to 7 split-K slices against its scratch
+     either way) is that one bit for bit.
   4. The split weights follow the parameters: three consecutive steps at lr 1e-3 (deferred output-layer
      Adam on and off) within rel 1e-4 of the fp32 oracle's BCE trajectory, then new parameters +
      sync_shadows: the next step equals a freshly built model's bit for bit.
@@ -158,7 +160,7 @@ def _refs(shape):
     return _CACHE[key]
 
 
-def _one_step(shape, prec, split=None):
+def _one_step(shape, prec, split=None, side_stream=None):
     """train_fwd_bwd + grad_norm + adam_step from zero moments; returns what the checks need."""
     from gm2 import native
     from gm2.data import ResidentMatrix
@@ -169,6 +171,8 @@ def _one_step(shape, prec, split=None):
     ws = m.workspace(prec, B)
     if split is not None:
         ws.set_option(native.OPT_TRAIN_SPLIT, split)
+    if side_stream is not None:
+        ws.set_option(native.OPT_SIDE_STREAM, side_stream)
     before = {k: ws.stat(v) for k, v in native.TRAIN_STATS.items()}
     grads = torch.zeros_like(m.params)
     loss = torch.zeros(native.LOSS_SLOTS, dtype=torch.float64, device="cuda")
@@ -231,12 +235,34 @@ def _check_step(shape, r, label):
 
 
 # ------------------------------------------------------------------------------ 3. one step, split path
+def _big_step():
+    """The step at BIG under default options: run once, read by the tests below."""
+    if "big_step" not in _CACHE:
+        from gm2 import native
+        _CACHE["big_step"] = _one_step(BIG, native.GM2_BF16X3)
+    return _CACHE["big_step"]
+
+
 def test_train_step_split_path():
-    from gm2 import native
-    r = _one_step(BIG, native.GM2_BF16X3)
+    r = _big_step()
     assert r["stats"] == {"split_gemms": 5, "exact_gemms": 0}, r["stats"]
     assert "bf16x3" in repr(r["m"])
     _check_step(BIG, r, "bf16x3")
+
+
+def test_train_step_side_stream_off_bit_identical():
+    """GM2_OPT_SIDE_STREAM = 0 at BIG, where the bf16x3 dW9 wants 8 split-K slices of 8200 x 256
+    floats and shrinks to the 7 its scratch holds: the same slice count in the same scratch as with
+    the side stream, so gradients, loss slots, BatchNorm running statistics and the updated
+    parameters are the side-stream run's bit for bit (itself held to the oracle above)."""
+    from gm2 import native
+    a = _big_step()
+    b = _one_step(BIG, native.GM2_BF16X3, side_stream=0)
+    assert b["stats"] == {"split_gemms": 5, "exact_gemms": 0}, b["stats"]
+    assert torch.equal(a["grads"], b["grads"])
+    assert np.array_equal(a["loss"], b["loss"])
+    assert torch.equal(a["bn"], b["bn"])
+    assert torch.equal(a["m"].params, b["m"].params)
 
 
 # ------------------------------------------------------------------------------ 4. weights are re-split
