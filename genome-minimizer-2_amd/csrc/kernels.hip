@@ -104,7 +104,9 @@ __global__ __launch_bounds__(256) void k_bn_fwd_partial(const float* __restrict_
   const int r0 = blockIdx.y * kBnRowChunk;
   const int nrows = min(kBnRowChunk, B - r0);
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float4 b = bias ? *(const float4*)(bias + col) : zero;
+  // (bias, like gamma / beta below, is a slice of the flat parameter buffer: 4-byte aligned only when
+  // the latent width is 1 or 2)
+  const float4 b = bias ? make_float4(bias[col], bias[col + 1], bias[col + 2], bias[col + 3]) : zero;
   // rows past nrows re-read the chunk's last row (never used): branch-free loads, and up to four
   // slabs' loads in flight together
   float4 v[8];
@@ -195,7 +197,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
   const int nrows = min(kBnRowChunk, B - r0);
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   const float4 mean = *(const float4*)(save + col), invstd = *(const float4*)(save + H + col);
-  const float4 gm = *(const float4*)(gamma + col), bt = *(const float4*)(beta + col);
+  const float4 gm = make_float4(gamma[col], gamma[col + 1], gamma[col + 2], gamma[col + 3]);
+  const float4 bt = make_float4(beta[col], beta[col + 1], beta[col + 2], beta[col + 3]);
   const float4 al = make_float4(invstd.x * gm.x, invstd.y * gm.y, invstd.z * gm.z, invstd.w * gm.w);
   const float4 bp = make_float4(fmaf(-mean.x, al.x, bt.x), fmaf(-mean.y, al.y, bt.y), fmaf(-mean.z, al.z, bt.z),
                                 fmaf(-mean.w, al.w, bt.w));
@@ -646,7 +649,10 @@ __device__ __forceinline__ void adam_block(const TensorDesc& d, int64_t blk, con
   const float aeps = scal[kScalAdamEps];
   const float cc = clip[0];
   T* sh = (T*)d.shadow;
-  if (e0 + 4096 <= numel) {
+  // a tensor whose flat offset is not a multiple of 4 (latent width 1 or 2: the tensors behind
+  // logvar_layer) has no 16-B aligned elements: it takes the element path below throughout
+  const bool al = (d.off & 3) == 0;
+  if (al && e0 + 4096 <= numel) {
     // whole block: all 16 loads of the thread in flight before the first update; every byte is
     // touched once per step, so loads and stores are non-temporal (streamed past the caches)
     float4 pv[4], gv[4], mv[4], vv[4];
@@ -697,7 +703,7 @@ __device__ __forceinline__ void adam_block(const TensorDesc& d, int64_t blk, con
     if (e >= numel) break;
     const int64_t gi = d.off + e;
     float4 pv, gv, mv, vv;
-    const bool full = e + 4 <= numel;
+    const bool full = al && e + 4 <= numel;
     if (full) {
       pv = *(const float4*)(p + gi);
       gv = *(const float4*)(g + gi);
@@ -1829,8 +1835,6 @@ void launch_adam_fused(const TensorTable& tt, const float* grads, float* params,
                        const float* clip, hipStream_t s, int max_grid, float* scal_copy) {
   const TensorDesc& last = tt.t[tt.n - 1];
   const int64_t blocks = last.tile0 + (last.rows * last.cols + 4095) / 4096;
-  for (int i = 0; i < tt.n; ++i)
-    if (tt.t[i].off % 4) throw Gm2Error("adam: tensor offset not 16-B aligned");
   const int64_t grid = max_grid > 0 ? std::min<int64_t>(blocks, max_grid) : blocks;
   TimedLaunch tl(kKcAdam, s);
   hipLaunchKernelGGL(k_adam_fused<T>, dim3((unsigned)grid), dim3(256), 0, s, tt, grads, params, m, v, scal, clip,

@@ -96,3 +96,100 @@ def scalars(beta=0.5, wgamma=0.0, lam=0.0, lr=1e-3, step=1, max_norm=1.0, b1=0.9
     v[native.S_MAX_NORM] = max_norm
     v[native.S_ONE_MINUS_B1], v[native.S_BETA2], v[native.S_ONE_MINUS_B2], v[native.S_ADAM_EPS] = 1 - b1, b2, 1 - b2, eps
     return torch.tensor(v, dtype=torch.float32).cuda()
+
+
+ADAM_U = 2.0 ** -24  # unit roundoff of fp32
+ADAM_K = 8           # roundings the kernel may stack on one quantity (tests/test_optimizer_cpu.py calibrates it)
+
+
+def adam_reference(p, g, m, v, scal, cc):
+    """One fused L1 + clip + Adam update (k_adam_fused) in float64, from the fp32 inputs, the fp32 scalar
+    block as the kernel reads it and the fp32 clip coefficient `cc`:
+        gg = (g + lam * sign(p)) * cc;  m' = m + w1 (gg - m);  v' = v * b2 + w2 * gg^2
+        den = sqrt(v') / bc2s + eps;    p' = p + negstep * m' / den
+    with per-element bounds on what the kernel's fp32 evaluation may differ by (u = 2^-24, K = 8: at
+    most eight roundings per quantity, sqrtf and the division correctly rounded, FMA contraction allowed):
+        tm = K u (|m| + |gg|);  tv = K u (v + gg^2)
+        tden = tv / (2 sqrt(v') bc2s) [0 where v' = 0] + K u den
+        tstep = |negstep| tm / den + step tden / den + K u step,  step = |negstep| |m'| / den
+        tp = 2 u |p'| + tstep
+    Returns {"p": (p', tp), "m": (m', tm), "v": (v', tv)} as float64 numpy arrays."""
+    p, g, m, v = (np.asarray(t, dtype=np.float32).astype(np.float64) for t in (p, g, m, v))
+    s = np.asarray(scal, dtype=np.float32).astype(np.float64)
+    lam, negstep, bc2s = s[native.S_LAMBDA], s[native.S_NEG_STEP], s[native.S_BC2_SQRT]
+    w1, b2, w2, eps = s[native.S_ONE_MINUS_B1], s[native.S_BETA2], s[native.S_ONE_MINUS_B2], s[native.S_ADAM_EPS]
+    cc = float(np.float32(cc))
+    u, K = ADAM_U, ADAM_K
+    gg = (g + lam * np.sign(p)) * cc
+    m2 = m + w1 * (gg - m)
+    v2 = v * b2 + w2 * gg * gg
+    rt = np.sqrt(v2)
+    den = rt / bc2s + eps
+    p2 = p + negstep * m2 / den
+    tm = K * u * (np.abs(m) + np.abs(gg))
+    tv = K * u * (v + gg * gg)
+    tden = np.where(v2 > 0, tv / np.where(v2 > 0, 2 * rt * bc2s, 1.0), 0.0) + K * u * den
+    step = abs(negstep) * np.abs(m2) / den
+    tstep = abs(negstep) * tm / den + step * tden / den + K * u * step
+    tp = 2 * u * np.abs(p2) + tstep
+    return {"p": (p2, tp), "m": (m2, tm), "v": (v2, tv)}
+
+
+def adam_inputs(n, seed, zeros=0.01):
+    """fp32 p, g, m, v of n elements for the optimizer tests: random signs, log-uniform magnitudes (|p| in
+    1e-4..1; |g|, |m|, sqrt(v) in 1e-8..1), with a share `zeros` of exact zeros in each and as many -0.0 in p."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+
+    def mag(lo):
+        return 10.0 ** rng.uniform(np.log10(lo), 0.0, n)
+
+    def sgn():
+        return np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    p, g, m, v = mag(1e-4) * sgn(), mag(1e-8) * sgn(), mag(1e-8) * sgn(), mag(1e-8) ** 2
+    for a in (p, g, m, v):
+        a[rng.random(n) < zeros] = 0.0
+    p[rng.random(n) < zeros] = -0.0
+    return tuple(a.astype(np.float32) for a in (p, g, m, v))
+
+
+def shadow_views(ws):
+    """Typed 2-D views of the eight GEMM weight shadows in ws.buf, by name. This mirrors make_layout in
+    csrc/api.hip, which takes them first, in this order, each region rounded up to 256 bytes:
+    sE0 [H][Gp], sE1 / sE2 [H][H], sHD [L2r][H] (rows 0..L-1 mean_layer, L..2L-1 logvar_layer), sD0 [H][Lr],
+    sD1 / sD2 [H][H], sD3 [Gp][H]; elements bf16 with Gp = roundup(G, 256) for GM2_BF16, fp32 with
+    Gp = roundup(G, 128) for GM2_F32 and GM2_BF16X3; L2r = roundup(2L, 128), Lr = roundup(roundup(L, 64), 128)."""
+    def up(x, k):
+        return (x + k - 1) // k * k
+    G, H, L = int(ws.d.G), int(ws.d.H), int(ws.d.L)
+    bf = ws.prec == native.GM2_BF16
+    dt, es = (torch.bfloat16, 2) if bf else (torch.float32, 4)
+    Gp, L2r, Lr = up(G, 256 if bf else 128), up(2 * L, 128), up(up(L, 64), 128)
+    shapes = [("sE0", H, Gp), ("sE1", H, H), ("sE2", H, H), ("sHD", L2r, H), ("sD0", H, Lr), ("sD1", H, H),
+              ("sD2", H, H), ("sD3", Gp, H)]
+    out, cur = {}, ws.off
+    for name, r, c in shapes:
+        out[name] = ws.buf[cur: cur + r * c * es].view(dt).view(r, c)
+        cur += up(r * c * es, 256)
+    return out
+
+
+# (parameter name, shadow region, first row) of the nine Linear weights (make_table in csrc/api.hip)
+SHADOW_OF = [("encoder.0.weight", "sE0", 0), ("encoder.3.weight", "sE1", 0), ("encoder.6.weight", "sE2", 0),
+             ("mean_layer.weight", "sHD", 0), ("logvar_layer.weight", "sHD", None), ("decoder.0.weight", "sD0", 0),
+             ("decoder.3.weight", "sD1", 0), ("decoder.6.weight", "sD2", 0), ("decoder.9.weight", "sD3", 0)]
+
+
+def expected_shadows(ws, params, specs, offsets):
+    """The image every shadow region must hold for the flat fp32 `params`: cvt(params) at [srow0 + r][c]
+    (cvt: identity for fp32 shadows, .bfloat16() for bf16 ones), zero everywhere else. CPU tensors shaped
+    and typed like shadow_views(ws)."""
+    views = shadow_views(ws)
+    pc = params.detach().cpu()
+    img = {k: torch.zeros(v.shape, dtype=v.dtype) for k, v in views.items()}
+    index = {n: i for i, (n, _) in enumerate(specs)}
+    for name, region, row0 in SHADOW_OF:
+        i = index[name]
+        r, c = specs[i][1]
+        row0 = int(ws.d.L) if row0 is None else row0
+        img[region][row0:row0 + r, :c] = pc[offsets[i]:offsets[i + 1]].view(r, c).to(img[region].dtype)
+    return img
