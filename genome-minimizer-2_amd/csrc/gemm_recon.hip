@@ -38,6 +38,13 @@ namespace {
 // bias arrives pre-scaled (nb = -b log2 e). BCE and sum(p) are summed per strain column and masked
 // once per column (padded strains).
 // Exact (fp32 parity) path: the reference's formula order, p computed first.
+// Where fp32 sigmoid(l) is subnormal (l in about (-88.72, -87.34)), as observed on an MI355X
+// (tests/test_gpu_loss_elements.py holds every path to bounds that contain both answers):
+//   exact paths (k_gemm_recon_loss<Small, float>, k_gemm_recon_loss_x3): p stays subnormal as in the
+//     reference, so a target of 1 gives BCE = |l| (87.5 .. 88.7) and dl = -p * 1e12 (~ -1e-26);
+//   FAST path (bf16, 128 and 256 tile): p comes out 0 (probed at -87.5, -88, -88.5, -88.7; at -87.3,
+//     where p is still normal, it is kept), so a target of 1 gives BCE = 100 (the clamp), dl = 0.
+// From l = -89 down (exp overflows) every path and the reference give p = 0, BCE = 100, dl = 0.
 // (m & a) | (~m & b) as one v_bfi_b32 (the compiler rewrites the C form into compare + select)
 __device__ __forceinline__ float bfi(int m, float a, float b) {
   float r;

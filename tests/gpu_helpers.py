@@ -193,3 +193,127 @@ def expected_shadows(ws, params, specs, offsets):
         row0 = int(ws.d.L) if row0 is None else row0
         img[region][row0:row0 + r, :c] = pc[offsets[i]:offsets[i + 1]].view(r, c).to(img[region].dtype)
     return img
+
+
+# ----------------------------------------------------------------------------------------------------
+# The loss epilogue (csrc/gemm_recon.hip) and the latent kernels (k_reparam, k_reparam_bwd), element by
+# element (tests/test_loss_elements_cpu.py calibrates both; tests/test_gpu_loss_elements.py uses them)
+# ----------------------------------------------------------------------------------------------------
+RECON_U = 2.0 ** -24                                  # unit roundoff of fp32
+RECON_FLT_MIN = float(np.finfo(np.float32).tiny)      # smallest normal fp32
+RECON_GUARD = float(np.float32(1e-12))                # the guard of BCE's backward, as fp32 holds it
+RECON_SAT_HI, RECON_SAT_LO = 17.5, -89.0              # l >= / <= these: every honest evaluation gives p == 1 / p == 0
+
+# the probe logits of the element tests, by regime. Left out on purpose: (15.5, 17.5), where 1 - p is one
+# to three ulps of p, so a 2-ulp hull contains p = 1 and with it both the -100 clamp and its absence; and
+# (-88.72, -89), the overflow edge of exp.
+RECON_PROBES = {
+    "ordinary": np.linspace(-12.0, 12.0, 97).astype(np.float32),
+    "approach": np.concatenate([np.linspace(12.25, 15.5, 14), np.linspace(-13.0, -27.0, 15),
+                                [-27.5, -27.63, -27.75, -28.0, -30.0, -40.0, -60.0, -80.0, -87.0]]).astype(np.float32),
+    "saturated": np.array([17.5, 18, 20, 30, 60, 88, 89, 100, 200, -89, -90, -103, -104, -200], dtype=np.float32),
+    "denormal": np.array([-87.5, -88.0, -88.5, -88.7], dtype=np.float32),
+}
+
+
+def _sigmoid64(l):
+    l = np.asarray(l, dtype=np.float64)
+    e = np.exp(-np.abs(l))
+    return np.where(l >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def _recon_formula64(p, x, wgamma):
+    """The reference's element formula in float64 from an fp32 p (exact in float64): BCE and dl."""
+    omp = 1.0 - p
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lg = np.where(x, np.log(p), np.log1p(-p))
+    bce = -np.maximum(lg, -100.0)
+    dl = ((p - x) / np.maximum(omp * p, RECON_GUARD) + wgamma) * omp * p
+    return bce, dl
+
+
+def recon_reference(l, x, wgamma, fast):
+    """Per-element float64 bounds of what the loss epilogue may return for fp32 logits `l` and 0/1 targets
+    `x` (numpy arrays of one shape): {"bce": (lo, hi), "p": (lo, hi), "dl": (lo, hi), "exact": mask,
+    "allow": {"bce": a, "p": 0, "dl": a}}.
+
+    The formula is the reference's (loss_components.py:49-50 through Sigmoid, autograd's BCE backward, the
+    gene-abundance term w*gamma per p): p = fp32 sigmoid, 1 - p formed from that fp32 p,
+        BCE = -max(log(x ? p : 1 - p), -100);  dl = ((p - x) / max((1 - p) p, 1e-12) + wgamma) (1 - p) p.
+    [lo, hi] is the hull of that formula, in float64, over the values of p an honest fp32 evaluation can
+    reach: p' = round32(sigmoid64(l')) and its neighbours within +-2 ulp (exact path: expf <= 1 ulp, the add
+    0.5 ulp, the division correctly rounded; FAST path: exp2, the add and rcp <= 1 ulp each), with l' = l
+    and, when `fast`, also l (1 +- 2 * 2^-23) (the FAST path forms acc * (-log2 e) + fp32(-b log2 e): two
+    roundings of a number of size |l| log2 e); and p' = 0 wherever round32(sigmoid64(l)) is subnormal
+    (hardware transcendentals flush, and expf itself overflows to p = 0 below -88.72). The hull is widened
+    by `allow`: 4 u |BCE| + 2^-22 (log(1 - p) for log1p(-p), a hardware log's absolute error near 1) and
+    8 u (|dl| + wgamma / 4) + FLT_MIN, u = 2^-24.
+
+    `exact`: l >= 17.5 (1 + e^-l rounds to 1: p == 1, BCE 0 for x = 1 and exactly 100 for x = 0, dl == 0 for
+    any wgamma) or l <= -89 (exp overflows: p == 0, BCE exactly 100 for x = 1 and 0 for x = 0, dl == +-0):
+    every honest evaluation gives that one value, lo == hi and nothing is allowed on top."""
+    l = np.asarray(l, dtype=np.float32)
+    xb = np.asarray(x) != 0
+    assert l.shape == xb.shape
+    l64 = l.astype(np.float64)
+    lps = [l64] + ([l64 * (1 + 2 * 2.0 ** -23), l64 * (1 - 2 * 2.0 ** -23)] if fast else [])
+    one, zero = np.float32(1), np.float32(0)
+    cands = []
+    for lp in lps:
+        p0 = _sigmoid64(lp).astype(np.float32)
+        up = dn = p0
+        cands.append(p0)
+        for _ in range(2):
+            up = np.minimum(np.nextafter(up, np.float32(2)), one)
+            dn = np.maximum(np.nextafter(dn, np.float32(-1)), zero)
+            cands += [up, dn]
+    flush = _sigmoid64(l64).astype(np.float32) < np.float32(RECON_FLT_MIN)
+    cands.append(np.where(flush, zero, cands[0]))
+    lo = {k: np.full(l.shape, np.inf) for k in ("bce", "p", "dl")}
+    hi = {k: np.full(l.shape, -np.inf) for k in ("bce", "p", "dl")}
+    for pc in cands:
+        p = pc.astype(np.float64)
+        bce, dl = _recon_formula64(p, xb, float(wgamma))
+        for k, v in (("bce", bce), ("p", p), ("dl", dl)):
+            lo[k] = np.minimum(lo[k], v)
+            hi[k] = np.maximum(hi[k], v)
+    sat1, sat0 = l >= np.float32(RECON_SAT_HI), l <= np.float32(RECON_SAT_LO)
+    exact = sat1 | sat0
+    val = {"bce": np.where(sat1 != xb, 100.0, 0.0), "p": np.where(sat1, 1.0, 0.0), "dl": np.zeros(l.shape)}
+    u = RECON_U
+    allow = {"bce": 4 * u * np.maximum(np.abs(lo["bce"]), np.abs(hi["bce"])) + 2.0 ** -22,
+             "p": np.zeros(l.shape),
+             "dl": 8 * u * (np.maximum(np.abs(lo["dl"]), np.abs(hi["dl"])) + abs(float(wgamma)) / 4) + RECON_FLT_MIN}
+    out = {"exact": exact, "allow": {}}
+    for k in ("bce", "p", "dl"):
+        a = np.where(exact, 0.0, allow[k])
+        out["allow"][k] = a
+        out[k] = (np.where(exact, val[k], lo[k] - a), np.where(exact, val[k], hi[k] + a))
+    return out
+
+
+# Rounding dl to bf16 (the bf16 paths store dL as bf16 and sum the stored values for the bias gradient): bf16
+# keeps 8 significant bits, so round-to-nearest-even moves a value by at most half an ulp = 2^-8 of it, reached
+# just above a power of two (1 + 2^-8 rounds to 1 or 1 + 2^-7), and by 2^-9 only just below one. (2^-9 is not a
+# bound: tests/test_loss_elements_cpu.py shows honest values beyond it.)
+BF16_RNE = 2.0 ** -8
+
+LATENT_K = 8  # roundings the latent kernels may stack on one quantity, as ADAM_K
+
+
+def latent_reference(mu, lv, beta):
+    """Per latent element, in float64 from the fp32 mu, logvar and beta, what k_reparam adds to loss slot 2
+    and what k_reparam_bwd returns for a zero upstream dz, each as (value, bound):
+        "kl":  1 + lv - mu^2 - exp(lv),     bound K u (1 + |lv| + mu^2 + exp(lv))
+        "dmu": beta mu,                     bound K u |beta mu|
+        "dlv": 0.5 beta (exp(lv) - 1),      bound K u 0.5 beta (1 + exp(lv))
+    u = 2^-24, K = 8. The bounds are absolute in the terms' sizes, so they cover the cancellation of
+    1 + lv - exp(lv) and of exp(lv) - 1 at lv near 0."""
+    mu = np.asarray(mu, dtype=np.float32).astype(np.float64)
+    lv = np.asarray(lv, dtype=np.float32).astype(np.float64)
+    beta = float(np.float32(beta))
+    ku = LATENT_K * RECON_U
+    ex = np.exp(lv)
+    return {"kl": (1 + lv - mu * mu - ex, ku * (1 + np.abs(lv) + mu * mu + ex)),
+            "dmu": (beta * mu, ku * np.abs(beta * mu)),
+            "dlv": (0.5 * beta * (ex - 1), ku * 0.5 * abs(beta) * (1 + ex))}

@@ -72,7 +72,8 @@ def test_gemm(prec, layout, M, N, K, splits, gemm_pp):
     pr = native.GM2_BF16 if prec == "bf16" else native.GM2_F32
     Pd, Qd = Ps.to(dt).cuda(), Qs.to(dt).cuda()
     C = torch.full((M, N), float("nan"), device="cuda")
-    slab = torch.empty(max(splits, 8) * M * N + 4, device="cuda") if splits != 1 else None
+    # (splits = -1: the plan's own count, up to 32 slices -- 16 for 512 x 512 x 8192 in either precision)
+    slab = torch.empty(max(splits, 32) * M * N + 4, device="cuda") if splits != 1 else None
     native.gemm(pr, Pd, Ps.shape[1], Qd, Qs.shape[1], C, N, M, N, K, splits, slab, pk, qk)
     ref = (P[:M].double() @ Q[:N].double().T)
     err = (C.cpu().double() - ref).abs().max().item()
