@@ -24,6 +24,196 @@ __device__ __forceinline__ double sq4(float a, float b, float c, float d) {
   return ((double)a * a + (double)b * b) + ((double)c * c + (double)d * d);
 }
 
+// stamp 3 of the probes (gemm_core.hpp): the tile's stores acknowledged
+__device__ __forceinline__ void stamp_end() {
+#ifdef GM2_STAMPS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  GM2_STAMP(3);
+#endif
+}
+
+template <int EPI, int BM>
+inline constexpr bool kRowEpi = BM == 128 && (EPI == 1 || EPI == 3 || EPI == 4);
+
+// combine the threads of a column through LDS and write the tile's BatchNorm partials (mode 1 / 2)
+template <class C>
+__device__ __forceinline__ void stats_tail(int bmode, const TileXY tl, int M, int N, int n, const float (&sa)[4],
+                                           const float (&sb)[4], const float (&sh)[4], const StoreEpi& bn,
+                                           char* smem) {
+  constexpr int TPR = C::BN / 4, RPI = C::NT / TPR;
+  float4* red = (float4*)smem;
+  red[2 * threadIdx.x] = make_float4(sa[0], sa[1], sa[2], sa[3]);
+  red[2 * threadIdx.x + 1] = make_float4(sb[0], sb[1], sb[2], sb[3]);
+  __syncthreads();
+  if (threadIdx.x < TPR && n < N) {
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), q = a;
+#pragma unroll
+    for (int k = 0; k < RPI; ++k) {
+      const float4 x = red[2 * (threadIdx.x + k * TPR)], y = red[2 * (threadIdx.x + k * TPR) + 1];
+      a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
+      q.x += y.x; q.y += y.y; q.z += y.z; q.w += y.w;
+    }
+    const float av[4] = {a.x, a.y, a.z, a.w}, qv[4] = {q.x, q.y, q.z, q.w};
+    float2* o = bn.part + (int64_t)(tl.m0 / C::BM) * bn.ldp + n;
+    const float nr = (float)min(C::BM, M - tl.m0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (bmode == 1) {
+        const float dm = av[u] / nr;
+        o[u] = make_float2(sh[u] + dm, fmaxf(fmaf(-av[u], dm, qv[u]), 0.f));
+      } else {
+        o[u] = make_float2(av[u], qv[u]);
+      }
+    }
+  }
+}
+
+// fixed-order block sum of the threads' sums of squares, one fp64 per tile (bn.sq; one K pass)
+template <class C>
+__device__ __forceinline__ void sq_tail(double sqa, const TileXY tl, int Np, const StoreEpi& bn, char* smem) {
+  double* red = (double*)smem;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const double w = wave_sum_d(sqa);
+  __syncthreads();
+  if (lane == 0) red[wid] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < C::NT / 64; ++k) t += red[k];
+    bn.sq[(tl.m0 / C::BM) * (Np / C::BN) + tl.n0 / C::BN] = t;
+  }
+}
+
+// The per-column operands of the row-store kinds: loaded before the main loop, used after it.
+struct RowCols {
+  float bb[4], mean[4], alpha[4], beta[4];
+};
+
+template <int EPI>
+__device__ __forceinline__ RowCols load_row_cols(int n, const float* __restrict__ bias, const StoreEpi& bn) {
+  RowCols cc;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    cc.bb[u] = (EPI == 3 && bias) ? bias[n + u] : 0.f;
+    cc.mean[u] = cc.alpha[u] = cc.beta[u] = 0.f;
+    if constexpr (EPI == 4) {
+      cc.mean[u] = bn.save[n + u];
+      cc.alpha[u] = bn.save[bn.H + n + u] * bn.gamma[n + u];
+      cc.beta[u] = fmaf(-cc.mean[u], cc.alpha[u], bn.beta[n + u]);
+    }
+  }
+  return cc;
+}
+
+// The row-store epilogues of the 128x128 tiles (EPI 1 / 3 / 4; host-checked: 16-B aligned rows, one
+// destination, N = Np). Same staging, values and summation order as the general code in store_tile
+// (per thread rows ascending within a band, bands ascending), but no trip to memory is waited for
+// between row passes: the passes are unrolled with rows past M predicated, a band's row stores go
+// out back to back, and mode 2's Y rows are all requested before the accumulators are staged, so
+// they land behind the staging and its barrier.
+template <class C, int EPI>
+__device__ __forceinline__ void store_rows(const TileXY tl, int M, int Np, float* __restrict__ Cz, int64_t ldc,
+                                           const StoreEpi& bn, const RowCols& cc, const f32x4 (&acc)[C::FM][C::FN],
+                                           char* smem) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wm = wid / C::WGN, wn = wid % C::WGN;
+  float* img = (float*)smem;
+  constexpr int pitch = C::BN + 4;
+  constexpr int BR = 64, NBANDS = C::BM / BR, BPW = C::WTM / BR;
+  constexpr int TPR = C::BN / 4, RPI = C::NT / TPR, NPASS = BR / RPI;
+  static_assert(BR * pitch * 4 <= C::LDS && C::NT % TPR == 0 && BR % RPI == 0 && 2 * C::NT * 16 <= C::LDS,
+                "epilogue shape");
+  const int cq = (threadIdx.x % TPR) * 4, rq = threadIdx.x / TPR;
+  const int n = tl.n0 + cq;
+  // mode 2: the thread's Y rows, requested before the staging -- all bands' at once where that is
+  // at most 8 float4 (the 8-wave tile), else band by band (the 4-wave tile: 8 per band)
+  constexpr bool YALL = NBANDS * NPASS <= 8;
+  float4 yv[NBANDS * NPASS];
+  auto load_y = [&](int h) {  // (rows past M: the last valid row's address, value unused)
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) {
+      const int m = min(tl.m0 + h * BR + rq + p * RPI, M - 1);
+      yv[h * NPASS + p] = *(const float4*)(bn.Y + (int64_t)m * bn.ldy + n);
+    }
+  };
+  if constexpr (EPI == 4 && YALL) {
+#pragma unroll
+    for (int h = 0; h < NBANDS; ++h) load_y(h);
+  }
+  float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
+  double sqa = 0.0;
+  // the bands of a tile with all BM rows valid (FULL: no predicate, so no branch around a store and
+  // the compiler's vmcnt for a Y row counts exactly the loads and stores issued after it) or not
+  auto bands = [&](auto full) {
+    constexpr bool FULL = decltype(full)::value;
+#pragma unroll
+    for (int h = 0; h < NBANDS; ++h) {
+      if constexpr (EPI == 4 && !YALL) load_y(h);
+      if (wm == h / BPW) {
+        const int mi0 = (h % BPW) * (BR / 16);
+#pragma unroll
+        for (int mi = 0; mi < BR / 16; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < C::FN; ++ni)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              img[(mi * 16 + 4 * (lane >> 4) + j) * pitch + wn * C::WTN + ni * 16 + (lane & 15)] = acc[mi0 + mi][ni][j];
+      }
+      __syncthreads();
+      if (EPI == 3 && h == 0) {  // shift = the tile's first row (always < M)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sh[u] = img[cq + u] + cc.bb[u];
+      }
+      float v[NPASS][4];
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const float4 w = *(const float4*)(img + (rq + p * RPI) * pitch + cq);
+        v[p][0] = w.x + cc.bb[0], v[p][1] = w.y + cc.bb[1], v[p][2] = w.z + cc.bb[2], v[p][3] = w.w + cc.bb[3];
+      }
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const int m = tl.m0 + h * BR + rq + p * RPI;
+        if (FULL || m < M) *(float4*)(Cz + (int64_t)m * ldc + n) = make_float4(v[p][0], v[p][1], v[p][2], v[p][3]);
+      }
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const bool ok = FULL || tl.m0 + h * BR + rq + p * RPI < M;
+        if constexpr (EPI == 1) {
+          const double q = sq4(v[p][0], v[p][1], v[p][2], v[p][3]);
+          sqa = ok ? sqa + q : sqa;
+        } else if constexpr (EPI == 3) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float dv = v[p][u] - sh[u];
+            sa[u] = ok ? sa[u] + dv : sa[u];
+            sb[u] = ok ? fmaf(dv, dv, sb[u]) : sb[u];
+          }
+        } else {
+          const float4 y4 = yv[h * NPASS + p];
+          float y[4] = {y4.x, y4.y, y4.z, y4.w};
+          // (ties the row's sign tests to its image read: hoisted to where Y lands, the masks of
+          // every row sat in SGPRs at once and spilled on the 4-wave tile)
+          asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]) : "v"(v[p][0]));
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float d = fmaf(y[u], cc.alpha[u], cc.beta[u]) > 0.f ? v[p][u] : 0.f;
+            sa[u] = ok ? sa[u] + d : sa[u];
+            sb[u] = ok ? fmaf(y[u] - cc.mean[u], d, sb[u]) : sb[u];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  };
+  if (tl.m0 + C::BM <= M) bands(std::true_type{});
+  else bands(std::false_type{});
+  if constexpr (EPI != 1) stats_tail<C>(EPI == 3 ? 1 : 2, tl, M, Np, n, sa, sb, sh, bn, smem);
+  if constexpr (EPI == 1) {
+    if (bn.sq) sq_tail<C>(sqa, tl, Np, bn, smem);
+  }
+}
+
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX, int EPI, bool S3>
 __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g, float* __restrict__ C0,
                                            float* __restrict__ C1, int msplit, int64_t ldc, int64_t slab,
@@ -36,6 +226,10 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
 // none): 0 = general (bias, BatchNorm statistics, row split, unaligned rows, transposed store),
 // 1 = plain fp32 store (split-K slabs or one pass, rows aligned or not, optional per-tile sums of
 // squares), 2 = the transposed store through the LDS image (+ sums of squares)
+// The 128x128 kernels take the row-store kinds (store_rows below: aligned whole rows, no row split,
+// no N edge; store_epi picks them on the host): 1 = plain or split-K slab store (+ sums of squares),
+// 3 = optional bias + forward BatchNorm statistics (mode 1), 4 = backward statistics (mode 2);
+// 0 stays the fallback for everything else
 // S3 (PP only; GM2_BF16X3 training): both operands in the split layout of k_split_kmajor / k_split_rows
 // (g.K = twice the real K) and the main loop in its hi.hi + hi.lo + lo.hi form
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX = 0, int EPI = 0, bool S3 = false>
@@ -72,6 +266,8 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
   const int nk = (kend - kbeg) / E<T>::KT;
   GM2_DBG(tl.m0 + C::BM <= g.Mp && tl.n0 + C::BN <= g.Np && kbeg >= 0 && kend <= g.K, kDbgTile);
   f32x4 acc[C::FM][C::FN];
+  RowCols cols;
+  if constexpr (kRowEpi<EPI, C::BM>) cols = load_row_cols<EPI>(tl.n0 + (threadIdx.x % (C::BN / 4)) * 4, bias_in, bn);
   if constexpr (PP) {
     int* sidx = (int*)(smem + C::LDS);
     if constexpr (IDX == 1) {
@@ -93,8 +289,13 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
     mainloop<C, T, AK, BK>(g.P, g.ldp, g.Q, g.ldq, tl.m0, tl.n0, kbeg, nk, smem, acc);
   }
   GM2_STAMP(2);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wm = wid / C::WGN, wn = wid % C::WGN;
   float* Cz = C0 + (int64_t)tl.split * slab;
+  if constexpr (kRowEpi<EPI, C::BM>) {
+    store_rows<C, EPI>(tl, g.M, g.Np, Cz, ldc, bn, cols, acc, smem);
+    stamp_end();
+    return;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wm = wid / C::WGN, wn = wid % C::WGN;
   // Stage one 64-row band of the tile at a time through the (now free) staging LDS (row pitch
   // BN + 4 floats: the accumulator writes of lanes 16 apart land 16 banks apart), then store whole
   // rows with 16-byte stores (4 columns per thread; scalar where C's rows are not 16-B aligned or
@@ -237,6 +438,8 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
     }
     __syncthreads();
   }
+  // (the two tails below: stats_tail and sq_tail spelt out -- calling the helpers here cost the
+  // 256x256 zero-copy kernel a spilled register)
   if (bmode) {  // (bn mode: N % 4 == 0, one K pass, 128-row tiles -- checked on the host)
     float4* red = (float4*)smem;
     red[2 * threadIdx.x] = make_float4(sa[0], sa[1], sa[2], sa[3]);
@@ -277,11 +480,7 @@ __device__ __forceinline__ void store_tile(const TileXY tl, const GemmArgs<T>& g
       bn.sq[(tl.m0 / C::BM) * (g.Np / C::BN) + tl.n0 / C::BN] = t;
     }
   }
-#ifdef GM2_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  GM2_STAMP(3);
-#endif
+  stamp_end();
 }
 
 }  // namespace
@@ -326,17 +525,28 @@ static void store_launch_k(const GemmArgs<T>& a, int tiles, const StoreOut& o, c
 }
 
 // the specialised epilogue a 256x256 launch can take (k_gemm_store EPI): 1 = plain fp32 store,
-// 2 = transposed through LDS, 0 = general
-static int store_epi(const GemmArgs<bf16_t>& a, const StoreOut& o, const StoreEpi& bn) {
+// 2 = transposed through LDS, 0 = general. A 128x128 launch (tile 128) takes a row-store kind where
+// the rows are 16-B aligned, go to one destination and the tile columns end at N: 1 = plain or slab
+// store, 3 = forward statistics (with or without bias), 4 = backward statistics; else 0
+template <typename T>
+static int store_epi(const GemmArgs<T>& a, const StoreOut& o, const StoreEpi& bn, int tile) {
   const bool aligned = ((o.ldc | o.slab) & 3) == 0 && (((uintptr_t)o.C0) & 15) == 0;
-  if (o.bias || bn.mode || (o.C1 && o.msplit < a.M)) return 0;
+  const bool split = o.C1 && o.msplit < a.M;
+  if (tile == 128) {
+    if (!aligned || split || bn.trans || a.N != a.Np) return 0;
+    if (bn.mode == 0) return o.bias ? 0 : 1;
+    if (bn.sq) return 0;
+    if (bn.mode == 1) return 3;
+    return o.bias || bn.ldy % 4 || (((uintptr_t)bn.Y) & 15) ? 0 : 4;
+  }
+  if (o.bias || bn.mode || split) return 0;
   if (bn.trans) return aligned ? 2 : 0;
   return 1;
 }
 
 template <class C, typename T, bool AK, bool BK, bool PP, int IDX>
 static void store_launch_epi(const GemmArgs<T>& a, int tiles, const StoreOut& o, const StoreEpi& bn, hipStream_t s) {
-  switch (store_epi(a, o, bn)) {
+  switch (store_epi(a, o, bn, 256)) {
     case 1: return store_launch_k<C, T, AK, BK, PP, IDX, 1>(a, tiles, o, bn, s);
     case 2:  // (launch_gemm_trans's one caller, the output-layer weight gradient, has no row table)
       if constexpr (IDX == 0) return store_launch_k<C, T, AK, BK, PP, 0, 2>(a, tiles, o, bn, s);
@@ -372,6 +582,14 @@ static void store_launch(const GemmArgs<T>& a, int tiles, const StoreOut& o, con
   }
   if (s3) throw Gm2Error("bf16x3 GEMM: bf16 256x256 tiles only");
   if (a.prow || a.qrow) throw Gm2Error("zero-copy rows: bf16 256x256 tiles only");
+  if constexpr (C::BM == 128) {
+    switch (store_epi(a, o, bn, 128)) {
+      case 1: return store_launch_k<C, T, AK, BK, false, 0, 1>(a, tiles, o, bn, s);
+      case 3: return store_launch_k<C, T, AK, BK, false, 0, 3>(a, tiles, o, bn, s);
+      case 4: return store_launch_k<C, T, AK, BK, false, 0, 4>(a, tiles, o, bn, s);
+      default: break;
+    }
+  }
   store_launch_k<C, T, AK, BK, false>(a, tiles, o, bn, s);
 }
 
